@@ -9,9 +9,14 @@
 One step = synthetic batch already in HBM -> forward -> kldiv -> backward ->
 (RCCL all-reduce of the flat gradient buffer when N > 1) -> fused Adam, all on the
 hand-written HIP kernels of libvinet_hip.so.  Weak scaling: the per-GPU batch is
-fixed.  Prints ONE JSON line on rank 0 with the roofline of the dominant kernel
-site (HIP events on the launch stream, measured inside the timed region) and the
-CPU baseline (PyTorch-CPU oracle on the box's host cores, rank 0, N == 1 only).
+fixed.  Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the
+K steps and reports the headline (`value` clips/s, `ms_per_step`) and nothing else.
+`--full` adds everything else the line used to carry: the roofline of the whole step
+and of the dominant kernel site (HIP events on the launch stream, measured inside
+the timed region), the batch sweeps, the inference / secondary-configuration legs,
+the CPU baseline (PyTorch-CPU oracle on the box's host cores, rank 0, N == 1 only)
+and the parity report.  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (float32).
 """
 import argparse
 import json
@@ -36,6 +41,7 @@ SWEEP_BATCHES = (1, 2, 4, 8, 16, 32)
 GLOBAL_BATCH_SWEEP = (64, 256, 1536)      # N > 1: global batches of the data-parallel sweep (8 / 32 / 192 clips per GPU at N = 8)
 # forward work per clip (inference): (clip, height, width) -> (GFLOP, MB)
 INFER_WORK = {(32, 224, 384): (229.32, 1004.9), (64, 256, 448): (611.5, 2664.8), (8, 128, 192): (16.36, 73.0), (8, 224, 384): (57.25, 255.5)}
+DUMP_SAMPLE = 4 << 20        # --dump-outputs: elements kept of a longer array (16 MB in float32; three arrays stay under 64 MB)
 
 
 def parse(argv=None):
@@ -66,6 +72,12 @@ def parse(argv=None):
     ap.add_argument("--cfg", default="", help="engine / library options, 'name=value,...' (vinet_amd.engine.configure; 'lib.<option>=<int>' reaches vinet_set_option); recorded in the result line")
     ap.add_argument("--force-collectives", action="store_true", help="treat a ONE-rank process group as distributed: every collective of the N > 1 path goes through RCCL (functional test on one GPU)")
     ap.add_argument("--dist-backend", default="", help="process-group backend (default: nccl = RCCL); tests use gloo on device tensors")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline: whole-step and per-kernel roofline (per-site "
+                    "HIP events), local / global batch sweeps, all-reduce timeline, inference and secondary-configuration legs, CPU "
+                    "baseline, parity report (--no-sweep / --no-extras / --no-cpu-baseline still drop parts of it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float32; training: loss, parameters after the update, gradients; inference: maps; a fixed seeded sample of "
+                    "%d elements of a longer array)" % DUMP_SAMPLE)
     return ap.parse_args(argv)
 
 
@@ -172,14 +184,14 @@ def main():
     _lib.load()
     engine.configure_from_string(args.cfg)
     out = measure(args, rank, world, dev)
-    if rank == 0 and world == 1 and args.mode == "train" and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and args.mode == "train" and not args.no_extras:
         import gc
         gc.collect()
         torch.cuda.empty_cache()
         out.update(extras(args, dev))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             out["parity"] = parity_block()
         except Exception as e:      # a report file that cannot be read must never cost the bench line
@@ -237,7 +249,7 @@ def parity_block():
 def _quiet(args, **kw):
     """a copy of the parsed arguments for a secondary leg: no sweep, no site table, no CPU baseline"""
     a = argparse.Namespace(**vars(args))
-    a.no_sweep, a.profile_all, a.no_cpu_baseline, a.no_extras = True, False, True, True
+    a.no_sweep, a.profile_all, a.no_cpu_baseline, a.no_extras, a.dump_outputs = True, False, True, True, ""
     for k, v in kw.items():
         setattr(a, k, v)
     return a
@@ -329,9 +341,54 @@ def extras(args, dev):
     return res
 
 
+def _max_over_ranks(seconds, dev):
+    """the slowest rank's time (every rank's timed region ends behind the same barrier)"""
+    from vinet_amd import parallel
+    t = torch.tensor([seconds], dtype=torch.float64, device=dev)
+    if parallel.distributed():
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return float(t)
+
+
+def headline(args, world, B, av, elapsed, dev):
+    """the fields of the result line that every run carries (rank 0)"""
+    from vinet_amd import engine
+    return {
+        "metric": ("clips/sec training (%dx%dx%d %s)" % (args.clip, args.height, args.width, args.dtype)) if args.mode == "train" else "inference clips/sec (one output frame per clip)",
+        "value": world * B * args.steps / elapsed, "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": ("AViNet (SoundNet + bilinear fusion)" if av else "ViNet DHF1K") + " %s, %dx%dx%d %s, %d clip(s)/GPU/step, kldiv + fused Adam, %s"
+                               % ("training" if args.mode == "train" else "inference", args.clip, args.height,
+                                  args.width, args.dtype, B,
+                                  "1xMI355X" if world == 1 else "%dxMI355X RCCL all-reduce" % world),
+                   "global_batch": world * B, "local_batch": B, "clip": [args.clip, args.height, args.width],
+                   "parallelism": "dp%d" % world,
+                   "engine": engine.config(changed_only=True),
+                   "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1),
+                   "reserved_hbm_gb": round(torch.cuda.memory_reserved(dev) / 1e9, 1)},
+    }
+
+
+def dump_outputs(path, result, opt):
+    """--dump-outputs: what a caller of the timed path holds after its LAST step, as float32 DIR/<name>.npy.  Training: `loss`,
+    `params` (the parameters after the Adam update) and `grads` (that step's gradients), both from the optimizer's flat fp32
+    buffers in parameter order; inference: `maps`.  An array of more than DUMP_SAMPLE elements is reduced to the same
+    elements in every run (seeded choice, ascending positions), so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": result, "params": opt.flat_p, "grads": opt.flat_g} if opt is not None else {"maps": result}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def measure(args, rank, world, dev):
     """one configuration: warm-up, dominant-kernel discovery, K timed steps -> the result dict (rank 0; other ranks get the
-    same dict without meaning)"""
+    same dict without meaning).  Without --full (or --profile-all): warm-up and the K timed steps only, the headline fields"""
     from vinet_amd import engine, loss, model, optim, parallel, synth
     engine.set_default_dtype(args.dtype)
     engine.WGRAD_SIDE_STREAM = not args.no_side_stream
@@ -357,9 +414,19 @@ def measure(args, rank, world, dev):
         opt = optim.Adam(parallel.trainable_parameters(m), lr=1e-4)
         parallel.broadcast_parameters(opt)
         buckets = parallel.GradientBuckets(opt)      # N > 1: bucketed RCCL all-reduce issued from the tape, overlapped with backward
-        buckets.timing = True                        # (two HIP events per 25 MB bucket: issue / completion stamps in the result line)
+        buckets.timing = args.full                   # (two HIP events per 25 MB bucket: issue / completion stamps in the result line)
+        # Every step starts from the same state: the synthetic weights and Adam's initial moments.  The weight gradients are summed
+        # with fp32 atomics (split-K), whose order varies from run to run; chained steps would carry that rounding into the next
+        # step's weights, and over the warm-up and timed steps bf16 training amplifies it far beyond rounding.  With the state
+        # restored, every step computes the same thing from the same inputs in every run (three device copies, ~0.4 GB, per step).
+        start = (opt.flat_p.clone(), opt.flat_m.clone(), opt.flat_v.clone(), opt._step)
 
         def train_step(ins, g_):
+            opt.flat_p.copy_(start[0])
+            opt.flat_m.copy_(start[1])
+            opt.flat_v.copy_(start[2])
+            opt._step = start[3]
+            engine.bump_weights_epoch()
             opt.zero_grad()
             buckets.begin_step()
             l = loss.kldiv(m(*ins), g_)
@@ -394,6 +461,20 @@ def measure(args, rank, world, dev):
         hp = torch.cuda.Stream(dev, priority=args.main_priority)
         hp.wait_stream(torch.cuda.current_stream(dev))
         torch.cuda.set_stream(hp)
+    if not (args.full or args.profile_all):
+        # ---- plain run: warm-up and the timed steps, nothing bracketed, nothing measured beside the headline
+        for _ in range(max(args.warmup, 1)):
+            step()
+        sync()
+        t0 = time.perf_counter()
+        last = None
+        for _ in range(args.steps):
+            last = step()
+        sync()
+        elapsed = _max_over_ranks(time.perf_counter() - t0, dev)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last, opt if args.mode == "train" else None)
+        return headline(args, world, B, av, elapsed, dev) if rank == 0 else {}
     # ---- warm-up; the last warm-up step is bracketed site by site to find the dominant kernel site
     graphed = args.mode == "infer" and args.graph
     for i in range(max(args.warmup, 1)):
@@ -476,15 +557,15 @@ def measure(args, rank, world, dev):
     engine.set_profiler(None if graphed else prof)
     sync()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     sync()
     t1 = time.perf_counter()
     engine.set_profiler(None)
-    elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
-    if parallel.distributed():
-        dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
-    elapsed = float(elapsed)
+    elapsed = _max_over_ranks(t1 - t0, dev)
+    if args.dump_outputs and rank == 0:      # (before the sweeps below take further steps)
+        dump_outputs(args.dump_outputs, last, opt if args.mode == "train" else None)
     # N > 1 (or --force-collectives): the gradient exchange of the LAST timed step -- per 25 MB bucket when its all-reduce
     # was issued and when it completed (ms from the start of the step), and how much of the exchange lay inside the backward pass
     comm = buckets.timeline() if (args.mode == "train" and parallel.distributed()) else None
@@ -682,23 +763,9 @@ def measure(args, rank, world, dev):
             roof = new_roof
         else:     # (inference legs, shapes without a SURVEY work figure: the dominant kernel's own roofline, as before)
             roof["top_kernels"] = top_kernels
-        out = {
-            "metric": ("clips/sec training (%dx%dx%d %s)" % (args.clip, args.height, args.width, args.dtype)) if args.mode == "train" else "inference clips/sec (one output frame per clip)",
-            "value": value, "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": ("AViNet (SoundNet + bilinear fusion)" if av else "ViNet DHF1K") + " %s, %dx%dx%d %s, %d clip(s)/GPU/step, kldiv + fused Adam, %s"
-                                   % ("training" if args.mode == "train" else "inference", args.clip, args.height,
-                                      args.width, args.dtype, B,
-                                      "1xMI355X" if world == 1 else "%dxMI355X RCCL all-reduce" % world),
-                       "global_batch": world * B, "local_batch": B, "clip": [args.clip, args.height, args.width],
-                       "parallelism": "dp%d" % world,
-                       "engine": engine.config(changed_only=True),
-                       "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1),
-                       "reserved_hbm_gb": round(torch.cuda.memory_reserved(dev) / 1e9, 1)},
-            "roofline": roof,
-            "whole_step": None if whole is None else {"hbm_frac_of_8TBs": whole["frac"], "mfma_frac_of_2.5PF": whole["mfma_frac"]},
-        }
+        out = headline(args, world, B, av, elapsed, dev)
+        out["roofline"] = roof
+        out["whole_step"] = None if whole is None else {"hbm_frac_of_8TBs": whole["frac"], "mfma_frac_of_2.5PF": whole["mfma_frac"]}
         if comm is not None:
             out["allreduce"] = dict(comm, payload_mb=round(opt.flat_g.numel() * 4 / 1e6, 1), bucket_mb=25,
                                     note="RCCL all-reduce (SUM) of the flat fp32 gradient buffer in reverse-order buckets, issued from inside "

@@ -30,6 +30,7 @@ import torch
 
 from vinet_amd import synth
 from oracle import vinet_cpu as O
+from tests import goldens as G     # G.save: fixtures over 1 MiB are stored in parts
 
 REF = "/root/reference"
 TOL_ORACLE = 2e-6  # oracle-vs-reference; observed 0.0 on every case
@@ -132,7 +133,7 @@ def block_case(name, make_ref, make_ora, in_shape, seed, out, compact=False):
                     _check("%s/train/%s" % (name, k), v, st_o[k], meta)
                     res["train_stat:" + k] = _np(v)
     res["meta"] = np.array(json.dumps(dict(meta, seed=seed, in_shape=list(in_shape), name=name)))
-    np.savez_compressed(os.path.join(out, "block_%s.npz" % name), **res)
+    G.save(os.path.join(out, "block_%s.npz" % name), **res)
     print("block", name, "ok", {k: v for k, v in list(meta["oracle_vs_reference_maxabs"].items())[:2]})
 
 
@@ -245,7 +246,7 @@ def decoder_case(RM, seed, out, clips=8):
         res["gp_head:" + k] = _np(g.reshape(-1)[:2048])
     res["head_w"], res["head_b"] = _np(w), _np(b)
     res["meta"] = np.array(json.dumps(dict(meta, seed=seed, shapes=[list(s) for s in shapes], clips=clips, head_w_key=wk, head_b_key=bk)))
-    np.savez_compressed(os.path.join(out, "decoder%d.npz" % clips), **res)
+    G.save(os.path.join(out, "decoder%d.npz" % clips), **res)
     print("decoder%d ok" % clips)
 
 
@@ -382,7 +383,7 @@ def train_step_case(RM, RL, seed, out, shape=(2, 8, 64, 96), name="train_step"):
         res["state:" + k] = _np(sd_r[k])
     res["head_w"], res["head_b"] = _np(sd[wk]), _np(sd[bk])
     res["meta"] = np.array(json.dumps(dict(meta, seed=seed, B=B, T=T, H=H, W=W, lr=1e-4, head_w_key=wk, head_b_key=bk)))
-    np.savez_compressed(os.path.join(out, name + ".npz"), **res)
+    G.save(os.path.join(out, name + ".npz"), **res)
     print("%s ok: loss %.6f -> %.6f" % (name, float(l0_r), float(l1_r)))
 
 
@@ -494,7 +495,7 @@ def trajectory_case(RM, RL, seed, out, steps=48, nb=4, shape=(8, 8, 128, 192), n
     res["head_w"], res["head_b"] = _np(sd[wk]), _np(sd[bk])
     res["meta"] = np.array(json.dumps(dict(meta, seed=seed, steps=steps, batches=nb, B=B, T=T, H=H, W=W, lr=1e-4, head_w_key=wk, head_b_key=bk,
                                            batch_seed_rule="seed + 100 * i")))
-    np.savez_compressed(os.path.join(out, name + ".npz"), **res)
+    G.save(os.path.join(out, name + ".npz"), **res)
     print("%s ok: loss %.6f -> %.6f over %d steps; eval(batch 0) %.6f -> %.6f" % (name, l_r[0], l_r[-1], steps, e0_r, e1_r))
 
 

@@ -228,7 +228,8 @@ def test_bench_self_spawn_path(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--spawn", "--steps", "2", "--warmup", "1", "--batch", "72",
-                          "--sweep-steps", "1", "--no-cpu-baseline", "--no-extras", "--force-collectives"], env=env, capture_output=True, text=True, timeout=900)
+                          "--sweep-steps", "1", "--no-cpu-baseline", "--no-extras", "--force-collectives", "--full"],
+                         env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["config"]["parallelism"] == "dp1"
@@ -246,3 +247,35 @@ def test_bench_self_spawn_path(tmp_path):
                                    backward_end_ms=ar["backward_end_ms"], buckets=ar["buckets"]))
 
 
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run times --steps steps and carries the headline only (the roofline, sweeps, extras, CPU baseline and
+    parity report belong to --full); --dump-outputs writes the last timed step's loss, updated parameters and gradients as
+    float32 .npy files, the parameters finite and the whole dump under 64 MB.  Every step starts from the same state, so a second
+    run with the same arguments computes the same thing: the same loss, and weights no further apart than the two opposite Adam
+    steps (lr = 1e-4 each) that the rounding of the atomically summed weight gradients can flip on a vanishing gradient."""
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dump, dump2 = tmp_path / "outputs", tmp_path / "outputs2"
+    for d in (dump2, dump):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                              "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["value"] > 0 and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert abs(line["value"] - 4 * 3 / (3 * line["ms_per_step"] / 1e3)) < 1e-6 * line["value"]
+    assert not {"roofline", "sweep", "inference", "cpu_baseline", "parity"} & set(line), sorted(line)
+    files = sorted(os.listdir(dump))
+    assert files == ["grads.npy", "loss.npy", "params.npy"], files
+    arrs = {f: np.load(dump / f) for f in files}
+    assert all(a.dtype == np.float32 for a in arrs.values())
+    assert sum(os.path.getsize(dump / f) for f in files) <= 64 << 20
+    assert arrs["loss.npy"].size == 1 and np.isfinite(arrs["loss.npy"]).all()
+    assert arrs["params.npy"].size == arrs["grads.npy"].size > 0 and np.isfinite(arrs["params.npy"]).all()
+    again = {f: np.load(dump2 / f) for f in files}
+    assert abs(float(again["loss.npy"]) - float(arrs["loss.npy"])) <= 1e-5 * abs(float(arrs["loss.npy"]))
+    assert float(np.abs(again["params.npy"] - arrs["params.npy"]).max()) <= 2.5e-4

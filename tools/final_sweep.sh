@@ -20,7 +20,7 @@ print("memory after step 4 / 24 (allocated, reserved GiB):", res)
 assert abs(res[0][0] - res[1][0]) < 0.05 and abs(res[0][1] - res[1][1]) < 1.0, "memory grows across steps"
 PY
 python bench.py --model avinet --no-sweep --no-cpu-baseline --steps 4 --warmup 2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('avinet', d['value'], d['ms_per_step'])"
-python bench.py --clip 64 --height 256 --width 448 --no-sweep --no-cpu-baseline --steps 3 --warmup 2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('config5', d['value'], d['ms_per_step'], d['roofline']['whole_step'])"
+python bench.py --full --clip 64 --height 256 --width 448 --no-sweep --no-cpu-baseline --steps 3 --warmup 2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('config5', d['value'], d['ms_per_step'], d['whole_step'])"
 python bench.py --mode infer --batch 64 --no-cpu-baseline --steps 6 --warmup 2 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('infer b64', d['value'])"
 python bench.py --mode infer --batch 1 --graph --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('infer b1 graph', d['value'])"
 python -m vinet_amd.generate_result --synthetic_frames 191 --allow_synthetic_weights 2>&1 | grep -i "fps\|frames" | tail -2

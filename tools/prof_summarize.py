@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the rocprofv3 outputs of tools/prof_run.sh (gpurun_out/prof_<tag>/) into the committed evidence:
+"""Turn the rocprofv3 outputs of tools/prof_run.sh ($PROF_OUT/prof_<tag>/, default prof_out/) into the committed evidence:
 profiles/<tag>_rocprofv3_kernel_stats.csv, <tag>_pmc_summary.json, pmc_traffic.json (read by bench.py)."""
 import collections
 import csv
@@ -13,7 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r1_v4"
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 64
-base = os.path.join(ROOT, "gpurun_out", "prof_" + tag)
+base = os.path.join(os.environ.get("PROF_OUT", os.path.join(ROOT, "prof_out")), "prof_" + tag)
 out = os.path.join(ROOT, "profiles")
 
 

@@ -8,7 +8,6 @@ Runs the `train_step_wc` problem (ViNet-8, B = 12, 8 x 128 x 192, tests/golden/t
 the relative L2 distance of every parameter gradient, in REVERSE module order (the loss end first): the first layer whose error
 jumps is where the backward pass of the split form goes wrong.
 """
-import json
 import os
 import sys
 
@@ -27,8 +26,8 @@ for a in sys.argv[1:]:
         fixture = a[10:]
 _lib.load()
 DEV = torch.device("cuda:0")
-z = np.load(os.path.join(ROOT, "tests", "golden", fixture + ".npz"))
-meta = json.loads(str(z["meta"]))
+from tests.goldens import load as load_golden     # (a fixture may be stored in parts)
+z, meta = load_golden(fixture)
 B, T, H, W = meta["B"], meta["T"], meta["H"], meta["W"]
 x = synth.clip(B, T, H, W, meta["seed"]).permute(0, 2, 1, 3, 4).to(DEV)
 gt = synth.gt_map(B, H, W, meta["seed"]).to(DEV)
