@@ -436,12 +436,21 @@ class Ctx:
         self.training = training
         self.tape = [] if record else None
         self.stream = _stream_for(device)
+        self._bnb = {}           # id(storage owner) -> [(c0, c1, partials, rows, root, marks)]: BN-backward partial sums that data gradients left
+        self._side_rr = -1       # weight-gradient stream the last job went to (jobs are dealt round robin)
+        self._begin_backward()
+
+    def _begin_backward(self, capturing=False):
+        """the state of one backward pass (run_backward; a fresh Ctx is ready for a standalone conv backward, ops.py)"""
+        self.capturing = capturing      # the pass runs inside a stream capture
+        self.side_used = False   # a weight-gradient stream got work: the pass ends with the main stream waiting for them
         self._side_keep = []
-        self._deferred = []
+        self._deferred = []      # weight-gradient jobs waiting for their (shared) join: _schedule_wgrad / flush_deferred
         self._unpack_jobs = []
         self._dw_plans = []
-        self._bnb = {}           # id(storage owner) -> [(c0, c1, partials, rows, root, marks)]: BN-backward partial sums that data gradients left
-        self.capturing = False
+        self._joined = False     # flush_deferred has joined every weight-gradient stream: its jobs skip their own join
+        self.bwd_cm = None       # on_stream() of the branch stream the pass is on (markers of model_utils._Mixed._fwd_joint_forked_train)
+        self._tape_left = len(self.tape) if self.tape else 0        # nodes still to run, the current one included
 
     @property
     def recording(self):
@@ -475,6 +484,9 @@ class Ctx:
         """k-th weight-gradient stream of this device (None on the CPU test double)"""
         if not WGRAD_SIDE_STREAM or self.device.type != "cuda":
             return None
+        return self._stream(k)
+
+    def _stream(self, k):
         st = _SIDE_STREAMS.get((self.device.index, k))
         if st is None:
             st = _SIDE_STREAMS[(self.device.index, k)] = torch.cuda.Stream(self.device)
@@ -494,17 +506,12 @@ class Ctx:
                 return None
             if not BRANCH_STREAMS_EAGER and not torch.cuda.is_current_stream_capturing():
                 return None
-        out = []
-        for k in ("b1", "b2"):
-            st = _SIDE_STREAMS.get((self.device.index, k))
-            if st is None:
-                st = _SIDE_STREAMS[(self.device.index, k)] = torch.cuda.Stream(self.device)
-            out.append(st)
-        return out
+        return [self._stream(k) for k in ("b1", "b2")]
 
-    def on_stream(self, st):
-        """with ctx.on_stream(st): launches (and torch allocations) go to `st`"""
-        return _OnStream(self, st)
+    def on_stream(self, st, fork=True):
+        """with ctx.on_stream(st): launches (and torch allocations) go to `st`; None = stay where you are (CPU test double, no
+        weight-gradient stream).  fork=False: not a branch fork (DBG_SPIN_FORK); weight-gradient streams have DBG_SPIN_SIDE"""
+        return _OnStream(self, st, fork)
 
     def side_streams(self):
         """every weight-gradient stream in use (N_SIDE_STREAMS of them; empty without a GPU)"""
@@ -547,54 +554,42 @@ class Ctx:
         """the packed weight gradients collected during this backward -> `.grad`, ONE launch behind the last weight-gradient
         kernel (on the weight-gradient stream); the device-side job table is cached per job list (pointers are stable:
         persistent workspaces, gradient views of the optimizer's flat buffer)"""
-        jobs, self._unpack_jobs = getattr(self, "_unpack_jobs", []), []
+        jobs, self._unpack_jobs = self._unpack_jobs, []
         if not jobs:
             return
         # A plan that ran twice in this backward (a module called twice in one forward) queued its job twice, but its
         # persistent workspace already holds the SUM of both weight gradients: one job per workspace, or two thread
         # groups of the launch would race on `grad += dw; dw = 0` over the same rows.
-        seen, uniq = set(), []
+        uniq = {}
         for j in jobs:
-            if j[0] not in seen:
-                seen.add(j[0])
-                uniq.append(j)
-        jobs = uniq
-        key = tuple(jobs)
+            uniq.setdefault(j[0], j)
+        key = jobs = tuple(uniq.values())
         ent = _UNPACK_TABLES.get(key)
         if ent is None:
             # (never evicted: a captured step has the table's address baked into its launch, and a table is a few KB)
             assert not self.capturing, "weight-gradient unpack table built inside a stream capture (warm the step up first)"
-            rows, off = [], 0
-            for dw, gw, N, Cin, ntaps, stem, numel in jobs:
-                rows.append([dw, gw, N, Cin, ntaps, stem, off, 0])
-                off += numel
-            rows.append([0, 0, 0, 0, 0, 0, off, 0])
-            ent = _UNPACK_TABLES[key] = (torch.tensor(rows, dtype=torch.int64).to(self.device), off)
+            ent = _UNPACK_TABLES[key] = pack_table([j + (0,) for j in jobs], self.device)     # (the same row format)
         table, total = ent
-        side = self.side_stream()
-        main_ptr = self.stream
-        with (torch.cuda.stream(side) if side is not None else _NullCtx()):
-            if side is not None:
-                self.stream = side.cuda_stream
-            try:
-                self.call("vinet_unpack_wgrad_multi", table.data_ptr(), len(jobs), total, 3, self.stream)
-            finally:
-                self.stream = main_ptr
+        with self.on_stream(self.side_stream(), fork=False):
+            self.call("vinet_unpack_wgrad_multi", table.data_ptr(), len(jobs), total, 3, self.stream)
+
+    def finish_backward(self):
+        """the tail of a backward pass (run_backward; one conv's standalone backward, ops.py): the weight-gradient jobs still
+        waiting, the unpack launch behind them, and the main stream (the optimizer, every buffer release that follows) behind
+        the weight-gradient streams if they got work"""
+        self.flush_deferred()
+        self.flush_unpack()
+        if self.side_used:
+            for st in self.side_streams():
+                torch.cuda.current_stream(self.device).wait_stream(st)
 
     def run_backward(self):
-        self.side_used = False
-        self._side_keep = []
-        self._deferred = []
-        self._unpack_jobs = []
-        self.capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        self._tape_left = len(self.tape)         # nodes still to run, the current one included
-        self._dw_plans = []
+        self._begin_backward(self.device.type == "cuda" and torch.cuda.is_current_stream_capturing())
         try:
             for fn in reversed(self.tape):
                 fn()
                 self._tape_left -= 1
-            self.flush_deferred()
-            self.flush_unpack()
+            self.finish_backward()
         except BaseException:
             # every weight-gradient kernel ADDS into its plan's persistent workspace, which only the unpack launch hands back
             # zeroed: a backward pass that dies between the two would leave a residue that every later step silently adds to
@@ -615,13 +610,7 @@ class Ctx:
             self._deferred, self._unpack_jobs = [], []
             self._side_keep, self._bnb, self.tape = [], {}, []
             raise
-        if getattr(self, "side_used", False):
-            # the optimizer (and every buffer release that follows) is ordered after the side stream
-            for st in self.side_streams():
-                torch.cuda.current_stream(self.device).wait_stream(st)
-        self._side_keep = []
-        self._bnb = {}
-        self.tape = []
+        self._side_keep, self._bnb, self.tape = [], {}, []
 
 
 # ----------------------------------------------------------------------------
@@ -799,6 +788,54 @@ class ConvPlan:
             return 32
         return rup(self.N if transpose else self.Cin, 32)
 
+    def promise(self, launch, folded=False, rows=None):
+        """(tline, tpad) a launch over this plan's taps promises (VinetConvDesc / VinetWgradDesc::tline).  The tap table lives on
+        the device, so the library cannot check the promise and a wrong one is a silently wrong result: this is the only place
+        that makes one, next to the tap tables it describes.  First match wins, (0, 0) without one:
+
+          launch         "fwd"                    "wgrad"                     taps
+          pointwise      (6, 0)                   --                          the single tap (0, 0, 0, slice 0)
+          folded stem    (2, 0)                   (2, 0)                      (0, kh, 0, kh): folded_taps
+          other stem     (0, 0)                   (0, 0)                      CONV_STEM
+          temporal       (1, pT)                  (1, pT)                     (k,1,1): tap kt is (kt - pT, 0, 0, kt)
+          spatial3       (5, 0)                   --                          3 x 3 spatial footprint, kt-major: fwd_taps
+          decoder        --                       (4, 0)                      kT x 3 x 3, padding (0,1,1), stride (kT,1,1)
+          "dgrad" (one stride phase, taps `rows`): tline 6 if pointwise, else 5 if spatial3, else 1 if temporal with consecutive
+          dt offsets and at most 64 taps, else 0; tpad = -(first dt offset) in that temporal case, else 0
+          "dgrad_fused" (all stride phases of a temporal data gradient in one launch): (3, pT)
+
+        The two ladders do NOT agree and each stays as it is: a plain 1x1x1 ConvPlan is pointwise and temporal, (6, 0) forward
+        but (1, 0) in its weight gradient; a JointConvPlan (temporal = False) promises (6, 0) and (0, 0); the decoder's convs
+        promise 5 forward and 4 in their weight gradient."""
+        if launch == "dgrad_fused":
+            return 3, self.p[0]
+        if launch == "dgrad":
+            offs = sorted(r_[0] for r_ in rows)
+            tline = self.temporal and offs == list(range(offs[0], offs[0] + len(offs))) and self.ntaps <= 64
+            tl = 1 if tline else 0
+            if self.spatial3:
+                dts = [r_[0] for r_ in rows]
+                assert all(abs(r_[1]) <= 1 and abs(r_[2]) <= 1 for r_ in rows) and dts == sorted(dts, key=dts.index)
+                assert all(dts[i] == dts[i - 1] or dts[i] not in dts[:i] for i in range(1, len(dts))), "equal-dt taps must be contiguous"
+                tl = 5
+            if self.pointwise:
+                assert rows == [(0, 0, 0, 0)]
+                tl = 6
+            return tl, (-offs[0] if tline else 0)
+        if launch == "fwd" and self.pointwise:
+            return 6, 0
+        if folded:
+            return 2, 0
+        if self.stem:
+            return 0, 0
+        if self.temporal:
+            return 1, self.p[0]
+        if launch == "fwd":
+            return (5, 0) if self.spatial3 else (0, 0)
+        if self.k[1:] == (3, 3) and self.p == (0, 1, 1) and self.s == (self.k[0], 1, 1):
+            return 4, 0
+        return 0, 0
+
     # ---- device-side constant tables --------------------------------------
     def _dev_taps(self, key, rows, device):
         k = (key, str(device))
@@ -835,19 +872,8 @@ class ConvPlan:
                 full = False
                 continue
             key = ("dg", in_dims, rT, rH, rW)
-            offs = sorted(r_[0] for r_ in rows)
-            tline = self.temporal and offs == list(range(offs[0], offs[0] + len(offs))) and self.ntaps <= 64
-            tl = 1 if tline else 0
-            if self.spatial3:
-                dts = [r_[0] for r_ in rows]
-                assert all(abs(r_[1]) <= 1 and abs(r_[2]) <= 1 for r_ in rows) and dts == sorted(dts, key=dts.index)
-                assert all(dts[i] == dts[i - 1] or dts[i] not in dts[:i] for i in range(1, len(dts))), "equal-dt taps must be contiguous"
-                tl = 5
-            if self.pointwise:
-                assert rows == [(0, 0, 0, 0)]
-                tl = 6
             phases.append(dict(taps=self._dev_taps(key, rows, device), ntaps=len(rows), Q=(QT, QH, QW), r=(rT, rH, rW),
-                               tline=tl, tpad=-offs[0] if tline else 0))
+                               promise=self.promise("dgrad", rows=rows)))
         covered = all(len(p_) == min(s, I) for p_, s, I in zip(per, self.s, in_dims))
         return phases, (full and covered)
 
@@ -1120,16 +1146,11 @@ def _param_grad(p):
     return p.grad
 
 
-def _conv_kernel_name(ctx, d):
+def _kernel_name(ctx, d):
     buf = C.create_string_buffer(96)
-    ctx.lib.vinet_conv3d_kernel_name(C.byref(d), buf, 96)
-    return buf.value.decode() or "conv"
-
-
-def _wgrad_kernel_name(ctx, wd):
-    buf = C.create_string_buffer(96)
-    ctx.lib.vinet_conv3d_wgrad_kernel_name(C.byref(wd), buf, 96)
-    return buf.value.decode() or "wgrad"
+    wgrad = isinstance(d, L.CWgradDesc)
+    (ctx.lib.vinet_conv3d_wgrad_kernel_name if wgrad else ctx.lib.vinet_conv3d_kernel_name)(C.byref(d), buf, 96)
+    return buf.value.decode() or ("wgrad" if wgrad else "conv")
 
 
 def _splitk_scratch(ctx, d):
@@ -1144,6 +1165,45 @@ def _splitk_scratch(ctx, d):
     return ws
 
 
+def _conv_desc(ctx, mode, xv, yv, odims, stride, omul, ooff, ntaps, taps, w, kp, pre, n_valid, promise, accumulate):
+    """THE VinetConvDesc of this file (forward, fused temporal data gradient, per-phase data gradient): everything but the
+    epilogue (out_scale / out_shift / act / stats: _run_conv; a data gradient leaves them zero), split-K scratch and bnb_*"""
+    d = L.CConvDesc()
+    d.dtype, d.out_dtype, d.mode = ctx.cdt, yv.dt, mode
+    d.x, d.y = xv.ct(), yv.ct()
+    d.oT, d.oH, d.oW = odims
+    d.sT, d.sH, d.sW = stride
+    d.omT, d.omH, d.omW = omul
+    d.ooT, d.ooH, d.ooW = ooff
+    d.ntaps, d.taps, d.w, d.Kp = ntaps, _ptr(taps), w.data_ptr(), kp
+    d.pre, d.n_valid, d.accumulate = pre, n_valid, accumulate
+    d.tline, d.tpad = promise           # (ConvPlan.promise)
+    return d
+
+
+def _set_bnb(d, zv, fwd, mean, invstd, c1=None, c2=None):
+    """bnb_* of a conv / weight-gradient descriptor: raw conv output z, its BatchNorm (+ReLU) and batch statistics (+ c1, c2)"""
+    d.bnb_z, d.bnb_ld, d.bnb_sB, d.bnb_fwd = zv.ptr(), zv.ld, zv.sB, fwd
+    d.bnb_mean, d.bnb_invstd = mean.data_ptr(), invstd.data_ptr()
+    if c1 is not None:
+        d.bnb_c1, d.bnb_c2 = c1.data_ptr(), c2.data_ptr()
+
+
+def _conv_prof(ctx, kernel, kind, plan, xv, M, ex, ey, ew, parts=1, suffix=""):
+    """(tag, work) of a conv-shaped launch for the profiler: `kernel` is a name or the descriptor the library names the kernel
+    of; ex / ey / ew the element sizes of the input-, output- and weight-shaped operands; `parts` launches share the work"""
+    tag = None
+    if PROFILER is not None:
+        tag = (kernel if isinstance(kernel, str) else _kernel_name(ctx, kernel)) + suffix + " | " + kind + " " + plan.site(xv)
+    nw = plan.N * plan.Cin * plan.ntaps
+    return tag, dict(flops=2.0 * M * nw / parts, bytes=float(xv.nvox * plan.Cin * ex + M * plan.N * ey + nw * ew) / parts)
+
+
+def _run_conv(ctx, d, out_scale, out_shift, act, stats, tag, work, splitk=False):
+    """the epilogue of a forward conv and its launch"""
+    d.out_scale, d.out_shift, d.act, d.stats = out_scale, out_shift, act, stats
+    ws = _splitk_scratch(ctx, d) if splitk else None        # (held until the launch is issued)
+    ctx.call("vinet_conv3d", C.byref(d), ctx.stream, tag=tag, work=work)
 
 
 def conv_forward(ctx, plan, x, bn=None, act=L.ACT_NONE, dst=None, out_dt=None, n_pad=None):
@@ -1156,86 +1216,73 @@ def conv_forward(ctx, plan, x, bn=None, act=L.ACT_NONE, dst=None, out_dt=None, n
     `dst`         : optional destination Act (channel / T slice of a concat buffer).
     `n_pad`       : store into a channel-padded output (N not a multiple of the vector width).
     """
-    lib_dt = ctx.dt
     _note_reader(ctx, x)
     want_plain = (MATERIALIZE_NT and x.scale is not None and ctx.dt != L.F32 and x.fold is None and not plan.stem and
                   plan.N * plan.ntaps >= MATERIALIZE_NT and x.v.dt == ctx.dt)
     xv = x.v
     folded = plan.stem and x.fold is not None
     if folded:
-        oT, oH, oW = xv.T, (x.fold[0] - 1) // 2 + 1, (x.fold[1] - 1) // 2 + 1
+        odims = xv.T, (x.fold[0] - 1) // 2 + 1, (x.fold[1] - 1) // 2 + 1
     else:
-        oT, oH, oW = plan.out_dims(xv.T, xv.H, xv.W)
+        odims = plan.out_dims(xv.T, xv.H, xv.W)
     Ny = plan.N if n_pad is None else n_pad
-    odt = lib_dt if out_dt is None else out_dt
     if dst is None:
-        dst = Act(View.alloc(xv.B, oT, oH, oW, Ny, odt, xv.device))
+        dst = Act(View.alloc(xv.B, odims[0], odims[1], odims[2], Ny, ctx.dt if out_dt is None else out_dt, xv.device))
     out = dst.v
-    scale_out, shift_out = dst.scale, dst.shift
-    mean_out, invstd_out = dst.mean, dst.invstd
+    given = (dst.scale, dst.shift, dst.mean, dst.invstd)     # per-channel vectors the caller reserved (slices of a concat's)
     dst.mean = dst.invstd = None        # (set below by the training-mode BatchNorm path only)
-    assert (out.B, out.T, out.H, out.W, out.C) == (xv.B, oT, oH, oW, Ny), "conv output view mismatch"
+    assert (out.B, out.T, out.H, out.W, out.C) == (xv.B,) + tuple(odims) + (Ny,), "conv output view mismatch"
     taps, ntaps = plan.folded_taps(ctx.device) if folded else plan.fwd_taps(ctx.device)
     w = plan.packed(ctx, False)
-
-    d = L.CConvDesc()
-    d.dtype, d.out_dtype, d.mode = ctx.cdt, out.dt, (L.CONV_STEM if (plan.stem and not folded) else L.CONV_GENERIC)
-    d.x, d.y = xv.ct(), out.ct()
-    d.oT, d.oH, d.oW = oT, oH, oW
-    d.sT, d.sH, d.sW = (1, 2, 1) if folded else plan.s
-    d.omT = d.omH = d.omW = 1
-    d.ooT = d.ooH = d.ooW = 0
-    d.ntaps, d.taps, d.w, d.Kp = ntaps, taps.data_ptr(), w.data_ptr(), plan.kp(False)
-    d.pre = x.affine()
-    d.accumulate = 0
-    d.n_valid = plan.N if Ny != plan.N else 0
-    if plan.pointwise:
-        d.tline = 6                         # the single tap (0, 0, 0, slice 0)
-    elif not folded and not plan.stem and plan.temporal:
-        d.tline, d.tpad = 1, plan.p[0]      # promise to the library (it cannot read the device-side tap table)
-    elif folded:
-        d.tline = 2                         # taps (0, kh, 0, kh): ConvPlan.folded_taps
-    elif plan.spatial3:
-        d.tline = 5                         # 3 x 3 spatial footprint, kt-major tap order: ConvPlan.fwd_taps
+    d = _conv_desc(ctx, L.CONV_STEM if (plan.stem and not folded) else L.CONV_GENERIC, xv, out, odims,
+                   (1, 2, 1) if folded else plan.s, (1, 1, 1), (0, 0, 0), ntaps, taps, w, plan.kp(False), x.affine(),
+                   plan.N if Ny != plan.N else 0, plan.promise("fwd", folded), 0)
     if want_plain and not ctx.lib.vinet_conv3d_applies_pre_once(C.byref(d)):
         # (the halo-tile kernel applies a pending BN + ReLU once per staged element: no materialisation pass for its layers)
         x = materialize(ctx, x)
         xv = x.v
         d.x, d.pre = xv.ct(), x.affine()
-    M = xv.B * oT * oH * oW
-    site = plan.site(xv)
-    es = ESIZE[lib_dt]
-    work = dict(flops=2.0 * M * plan.N * plan.Cin * plan.ntaps,
-                bytes=float(xv.nvox * plan.Cin * es + M * plan.N * ESIZE[out.dt] + plan.N * plan.Cin * plan.ntaps * es))
-    conv_tag = _conv_kernel_name(ctx, d) + " | fwd " + site if PROFILER is not None else None
+    M = xv.B * odims[0] * odims[1] * odims[2]
+    es = ESIZE[ctx.dt]
+    tag, work = _conv_prof(ctx, d, "fwd", plan, xv, M, es, ESIZE[out.dt], es)
 
     train_bn = bn is not None and ctx.training
     keep = {}
     res = dst
     res.needs_grad = True
     if bn is None:
-        d.out_scale, d.out_shift = None, _ptr(plan.bias)
-        d.act, d.stats = act, None
-        ws = _splitk_scratch(ctx, d)
-        ctx.call("vinet_conv3d", C.byref(d), ctx.stream, tag=conv_tag, work=work)
+        _run_conv(ctx, d, None, _ptr(plan.bias), act, None, tag, work, splitk=True)
         res.scale = res.shift = None
         res.relu = False
         res.act_out = act
-    elif not train_bn:
-        scale = ctx.f32(plan.N) if scale_out is None else scale_out
-        shift = ctx.f32(plan.N) if shift_out is None else shift_out
+    elif train_bn:
+        rows = ctx.lib.vinet_conv3d_stats_rows(C.byref(d))
+        stats = ctx.f32(rows * 2 * plan.N)
+        _run_conv(ctx, d, None, _ptr(plan.bias), L.ACT_NONE, stats.data_ptr(), tag, work)
+        scale, shift, mean, invstd = (ctx.f32(plan.N) if g is None else g for g in given)
+        if rows >= 1024:        # tall table (early, high-resolution layers): coalesced pre-reduction to 256 rows
+            per = (rows + 255) // 256
+            rows2 = (rows + per - 1) // per
+            stats2 = ctx.f32(rows2 * 2 * plan.N)
+            ctx.call("vinet_bn_partials_fold", stats.data_ptr(), rows, plan.N, stats2.data_ptr(), rows2, ctx.stream)
+            stats, rows = stats2, rows2
+        bn.finalize(ctx, stats, rows, plan.N, M, mean, invstd, scale, shift)
+        res.scale, res.shift, res.relu = scale, shift, (act == L.ACT_RELU)
+        keep.update(mean=mean, invstd=invstd)
+        res.mean, res.invstd = mean, invstd      # (a consumer's data gradient may fold this BatchNorm's backward reduce pass in: _data_grad)
+    else:
+        scale, shift = (ctx.f32(plan.N) if g is None else g for g in given[:2])
         if ctx.recording:
             # eval-mode BN with gradients: keep the raw conv output (+bias), BN(+ReLU) stays pending
             assert not isinstance(bn, JointBN), "joint convs are not recorded under eval-mode BN"
             invstd = ctx.f32(plan.N)
             bn.fold(ctx, None, plan.N, scale, shift, invstd)
-            d.out_scale, d.out_shift, d.act, d.stats = None, _ptr(plan.bias), L.ACT_NONE, None
-            ctx.call("vinet_conv3d", C.byref(d), ctx.stream, tag=conv_tag, work=work)
+            _run_conv(ctx, d, None, _ptr(plan.bias), L.ACT_NONE, None, tag, work)
             res.scale, res.shift, res.relu = scale, shift, (act == L.ACT_RELU)
             keep.update(mean=bn.rm, invstd=invstd)
         else:
             cached = None
-            if scale_out is None and shift_out is None and bn.fold_cache is not None:
+            if given[0] is None and given[1] is None and bn.fold_cache is not None:
                 stamp = bn.fold_stamp(plan.bias, ctx.dt, ctx.device)
                 cached = bn.fold_cache.get("fold")
                 if cached is not None and cached[0] == stamp:
@@ -1245,30 +1292,9 @@ def conv_forward(ctx, plan, x, bn=None, act=L.ACT_NONE, dst=None, out_dt=None, n
                     bn.fold_cache["fold"] = (stamp, scale, shift)
             if cached is None:
                 bn.fold(ctx, plan.bias, plan.N, scale, shift)
-            d.out_scale, d.out_shift, d.act, d.stats = scale.data_ptr(), shift.data_ptr(), act, None
-            ws = _splitk_scratch(ctx, d)
-            ctx.call("vinet_conv3d", C.byref(d), ctx.stream, tag=conv_tag, work=work)
+            _run_conv(ctx, d, scale.data_ptr(), shift.data_ptr(), act, None, tag, work, splitk=True)
             res.scale = res.shift = None
             res.relu = False
-    else:
-        rows = ctx.lib.vinet_conv3d_stats_rows(C.byref(d))
-        stats = ctx.f32(rows * 2 * plan.N)
-        d.out_scale, d.out_shift, d.act, d.stats = None, _ptr(plan.bias), L.ACT_NONE, stats.data_ptr()
-        ctx.call("vinet_conv3d", C.byref(d), ctx.stream, tag=conv_tag, work=work)
-        scale = ctx.f32(plan.N) if scale_out is None else scale_out
-        shift = ctx.f32(plan.N) if shift_out is None else shift_out
-        mean = ctx.f32(plan.N) if mean_out is None else mean_out
-        invstd = ctx.f32(plan.N) if invstd_out is None else invstd_out
-        if rows >= 1024:        # tall table (early, high-resolution layers): coalesced pre-reduction to 256 rows
-            per = (rows + 255) // 256
-            rows2 = (rows + per - 1) // per
-            folded = ctx.f32(rows2 * 2 * plan.N)
-            ctx.call("vinet_bn_partials_fold", stats.data_ptr(), rows, plan.N, folded.data_ptr(), rows2, ctx.stream)
-            stats, rows = folded, rows2
-        bn.finalize(ctx, stats, rows, plan.N, M, mean, invstd, scale, shift)
-        res.scale, res.shift, res.relu = scale, shift, (act == L.ACT_RELU)
-        keep.update(mean=mean, invstd=invstd)
-        res.mean, res.invstd = mean, invstd      # (a consumer's data gradient may fold this BatchNorm's backward reduce pass in: _conv_backward)
 
     if ctx.recording:
         ctx.record(lambda: _conv_backward(ctx, plan, x, res, bn, act, train_bn, keep, M))
@@ -1276,32 +1302,28 @@ def conv_forward(ctx, plan, x, bn=None, act=L.ACT_NONE, dst=None, out_dt=None, n
 
 
 class _OnStream:
-    def __init__(self, ctx, st):
-        self.ctx, self.st = ctx, st
+    """Ctx.on_stream"""
+
+    def __init__(self, ctx, st, fork):
+        self.ctx, self.st, self.fork = ctx, st, fork
 
     def __enter__(self):
+        if self.st is None:
+            return self
         self.prev = self.ctx.stream
         self.cm = torch.cuda.stream(self.st)
         self.cm.__enter__()
         self.ctx.stream = self.st.cuda_stream
-        if DBG_SPIN_FORK and self.ctx.device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
+        if DBG_SPIN_FORK and self.fork and self.ctx.device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
             # schedule stress: the branch stream (> 0) or the forking stream (< 0) idles first, so the streams drift apart
             self.ctx.lib.vinet_debug_spin(abs(DBG_SPIN_FORK), self.st.cuda_stream if DBG_SPIN_FORK > 0 else self.prev)
         return self
 
     def __exit__(self, *exc):
+        if self.st is None:
+            return False
         self.ctx.stream = self.prev
         return self.cm.__exit__(*exc)
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
 
 
 def _split_planes_folded(ctx, x):
@@ -1346,6 +1368,7 @@ def _split_planes(ctx, x, dy, dy_planes=None):
 
 
 def _wgrad_desc(ctx, plan, x, dy, dw=None):
+    """THE VinetWgradDesc of this file (max_cus and bnb_* are the caller's)"""
     folded = plan.stem and x.fold is not None
     taps, ntaps = plan.folded_taps(ctx.device) if folded else plan.fwd_taps(ctx.device)
     wd = L.CWgradDesc()
@@ -1354,301 +1377,277 @@ def _wgrad_desc(ctx, plan, x, dy, dw=None):
     wd.sT, wd.sH, wd.sW = (1, 2, 1) if folded else plan.s
     wd.ntaps, wd.taps, wd.dw, wd.Kp = ntaps, taps.data_ptr(), (dw.data_ptr() if dw is not None else None), plan.kp(False)
     wd.pre = x.affine()
-    # a purely temporal kernel (k,1,1): tap kt is (kt - pad, 0, 0, kt) -- the library cannot read the
-    # device-side tap table, so the geometry is promised here (include/vinet_hip.h: tline)
-    if not folded and not plan.stem and plan.temporal:
-        wd.tline, wd.tpad = 1, plan.p[0]
-    elif folded:
-        wd.tline = 2        # taps (0, kh, 0, kh): ConvPlan.folded_taps
-    elif not plan.stem and plan.k[1:] == (3, 3) and plan.p == (0, 1, 1) and plan.s == (plan.k[0], 1, 1):
-        wd.tline = 4        # kT x 3 x 3, temporal stride = kT (the decoder): ConvPlan.fwd_taps order
+    wd.tline, wd.tpad = plan.promise("wgrad", folded)
     wd._keep = taps
     return wd
 
 
 def _conv_backward(ctx, plan, x, res, bn, act, train_bn, keep, M):
-    out = res.v
+    """backward of one conv_forward in four stages: dz -> dy through BatchNorm / activation, bias, weight and data gradient"""
     dz = res.grad_view()
     assert res.is_grad_ready(), "conv backward reached before any consumer produced a gradient"
-    Ny = out.C
-    fused_bnb = None
-    dy_planes = None        # fp32s: (hi, lo) planes of dy written by the BatchNorm-backward apply pass
-    # ---- through BN / activation: dz -> dy (w.r.t. the raw conv output) --------
+    fused_bnb = dy_planes = None
     if bn is not None:
-        fwd = res.affine()
-        nb = float(dz.nvox * dz.C * ESIZE[dz.dt])
-        # per BatchNorm behind this conv (one, or the members of a joint entry conv): its two backward sums either came with the
-        # gradient -- the data gradient that wrote dz LAST left their partial rows (VinetConvDesc::bnb_*; _find_bnb checks that
-        # no writer came after it) -- or need a reduce pass over (dz, z)
-        members = list(zip(bn.members, bn.offs, bn.widths)) if isinstance(bn, JointBN) else [(bn, 0, Ny)]
-        c1, c2 = ctx.f32(Ny), ctx.f32(Ny)
-        left = []
-        for m_, o_, w_ in members:
-            part = _find_bnb(ctx, res, o_, w_) if DGRAD_BN_STATS else None
-            if part is None:
-                left.append((m_, o_, w_))
-            else:
-                m_.bwd_finalize(ctx, part[0], part[1], w_, M, res.scale, train_bn, keep["invstd"], c1, c2, off=o_, ld=part[3], ws_off=part[2])
-        if len(left) == len(members):       # nothing came with the gradient: ONE pass over the whole tensor
-            rows = ctx.lib.vinet_stats_rows(C.byref(dz.ct()))
-            ws = ctx.f32(rows * 2 * Ny)
-            ctx.call("vinet_bn_bwd_reduce", C.byref(dz.ct()), C.byref(out.ct()), dz.dt, fwd, keep["mean"].data_ptr(),
-                     keep["invstd"].data_ptr(), ws.data_ptr(), ctx.stream,
-                     tag=("vinet_bn_bwd_reduce | C%d x %d voxels" % (dz.C, dz.nvox)) if PROFILER is not None else None,
-                     work=dict(flops=0.0, bytes=2 * nb))
-            for m_, o_, w_ in left:
-                m_.bwd_finalize(ctx, ws, rows, w_, M, res.scale, train_bn, keep["invstd"], c1, c2, off=o_, ld=Ny)
-        else:
-            for m_, o_, w_ in left:         # (a joint conv: the members whose gradient has several writers)
-                dzs, outs = dz.chan(o_, o_ + w_), out.chan(o_, o_ + w_)
-                rows = ctx.lib.vinet_stats_rows(C.byref(dzs.ct()))
-                ws = ctx.f32(rows * 2 * w_)
-                fsl = L.CAffine(res.scale.data_ptr() + 4 * o_, res.shift.data_ptr() + 4 * o_, 1 if res.relu else 0)
-                ctx.call("vinet_bn_bwd_reduce", C.byref(dzs.ct()), C.byref(outs.ct()), dz.dt, fsl, keep["mean"].data_ptr() + 4 * o_,
-                         keep["invstd"].data_ptr() + 4 * o_, ws.data_ptr(), ctx.stream,
-                         tag=("vinet_bn_bwd_reduce | C%d x %d voxels" % (w_, dz.nvox)) if PROFILER is not None else None,
-                         work=dict(flops=0.0, bytes=2 * nb * w_ / Ny))
-                m_.bwd_finalize(ctx, ws, rows, w_, M, res.scale, train_bn, keep["invstd"], c1, c2, off=o_, ld=w_, ws_off=0)
-        # A conv whose input needs no gradient (the RGB stem) has one consumer of dz, its weight gradient: kernels
-        # that can form dz from (gradient behind the BN, raw conv output) on the fly spare the apply pass
-        if BN_BWD_FUSE and not x.needs_grad and plan.wants_wgrad() and plan.bias is None and out.dt == dz.dt == ctx.dt:
-            q = _wgrad_desc(ctx, plan, x, dz)
-            q.bnb_z, q.bnb_ld, q.bnb_sB, q.bnb_fwd = out.ptr(), out.ld, out.sB, fwd
-            q.bnb_mean, q.bnb_invstd = keep["mean"].data_ptr(), keep["invstd"].data_ptr()
-            q.bnb_c1, q.bnb_c2 = c1.data_ptr(), c2.data_ptr()
-            if ctx.lib.vinet_conv3d_wgrad_fuses_bn_bwd(C.byref(q)):
-                fused_bnb = (out, fwd, keep["mean"], keep["invstd"], c1, c2)
-        if (fused_bnb is None and SPLIT_IN_APPLY and SPLIT_WGRAD_BF16 and ctx.cdt == F32S and plan.wants_wgrad() and dz.dt == F32 and
-                out.dt == F32 and dz.C % 8 == 0 and dz.ld % 8 == 0 and out.ld % 8 == 0 and ctx.device.type == "cuda"):
-            # fp32s: the hi / lo planes of dy (an operand of the three bf16 weight-gradient launches) leave with the apply pass
-            dh = View.alloc(dz.B, dz.T, dz.H, dz.W, dz.C, BF16, dz.device)
-            dl = View.alloc(dz.B, dz.T, dz.H, dz.W, dz.C, BF16, dz.device)
-            ctx.call("vinet_bn_bwd_apply_split", C.byref(dz.ct()), C.byref(out.ct()), fwd, keep["mean"].data_ptr(),
-                     keep["invstd"].data_ptr(), c1.data_ptr(), c2.data_ptr(), C.byref(dz.ct()), C.byref(dh.ct()), C.byref(dl.ct()), ctx.stream,
-                     tag=("vinet_bn_bwd_apply | C%d x %d voxels" % (dz.C, dz.nvox)) if PROFILER is not None else None,
-                     work=dict(flops=0.0, bytes=4 * nb))
-            dy_planes = (dh, dl)
-        elif fused_bnb is None:
-            ctx.call("vinet_bn_bwd_apply", C.byref(dz.ct()), C.byref(out.ct()), dz.dt, fwd, keep["mean"].data_ptr(),
-                     keep["invstd"].data_ptr(), c1.data_ptr(), c2.data_ptr(), C.byref(dz.ct()), ctx.stream,
-                     tag=("vinet_bn_bwd_apply | C%d x %d voxels" % (dz.C, dz.nvox)) if PROFILER is not None else None,
-                     work=dict(flops=0.0, bytes=3 * nb))
-        dy = dz
-    elif act == L.ACT_RELU and res.grad_masked == res.root().grad_marks and dz.dt == ctx.dt:
-        dy = dz         # the only writer of dz (the upsample's backward) already gated it with this ReLU
-    elif act != L.ACT_NONE:
-        if dz.dt == ctx.dt:
-            dy = dz
-        else:
-            dy = View.alloc(dz.B, dz.T, dz.H, dz.W, dz.C, ctx.dt, dz.device)
-        ctx.call("vinet_act_bwd", C.byref(dz.ct()), dz.dt, C.byref(out.ct()), out.dt, act, C.byref(dy.ct()), dy.dt, ctx.stream)
+        dy, fused_bnb, dy_planes = _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz)
     else:
-        dy = dz
-        if dz.dt != ctx.dt:
-            dy = View.alloc(dz.B, dz.T, dz.H, dz.W, dz.C, ctx.dt, dz.device)
-            ctx.call("vinet_copy_affine", C.byref(dz.ct()), dz.dt, L.CAffine(None, None, 0), C.byref(dy.ct()), dy.dt, 0, ctx.stream)
-    # ---- bias ------------------------------------------------------------------
+        dy = _act_backward(ctx, res, act, dz)
     if plan.bias is not None and plan.bias.requires_grad:
-        rows = ctx.lib.vinet_stats_rows(C.byref(dy.ct()))
-        ws = ctx.f32(rows * 2 * Ny)
-        gb = _param_grad(plan.bias)
-        # channel-padded head: pad-channel gradients are exactly zero, so folding
-        # channels modulo N leaves the real sums untouched
-        assert Ny % plan.N == 0 and (Ny == plan.N or plan.N == 1)
-        ctx.call("vinet_channel_sum", C.byref(dy.ct()), dy.dt, ws.data_ptr(), plan.N, gb.data_ptr(), 1, ctx.stream)
-        _note_param_grad(ctx, plan.bias)
-    # ---- weight gradient (side stream) ---------------------------------------------
+        _bias_grad(ctx, plan, dy)
     if plan.wants_wgrad():
         for w_ in plan.grad_targets():
             _param_grad(w_)          # (allocated on the main stream, not inside the side-stream context)
+        _schedule_wgrad(ctx, _WgradJob(ctx, plan, x, dy, M, bn is None, fused_bnb, dy_planes))
+    if x.needs_grad:
+        _data_grad(ctx, plan, x, res.v, dy, M)
 
+
+def _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz):
+    """stage 1 behind a BatchNorm: dz (w.r.t. the BN + ReLU output) -> dy (w.r.t. the raw conv output), in place.  Returns
+    (dy, fused, planes): `fused` = (z, forward affine, mean, invstd, c1, c2) when the weight-gradient kernel forms dy on the fly
+    and no apply pass ran (else None); `planes` = the fp32s (hi, lo) bf16 planes of dy the apply pass wrote (else None)"""
+    out, Ny = res.v, res.v.C
+    fwd = res.affine()
+    mean, invstd = keep["mean"], keep["invstd"]
+    nb = float(dz.nvox * dz.C * ESIZE[dz.dt])
+    # per BatchNorm behind this conv (one, or the members of a joint entry conv): its two backward sums either came with the
+    # gradient -- the data gradient that wrote dz LAST left their partial rows (VinetConvDesc::bnb_*; _find_bnb checks that
+    # no writer came after it) -- or need a reduce pass over (dz, z)
+    members = list(zip(bn.members, bn.offs, bn.widths)) if isinstance(bn, JointBN) else [(bn, 0, Ny)]
+    c1, c2 = ctx.f32(Ny), ctx.f32(Ny)
+    left = []
+    for m_, o_, w_ in members:
+        part = _find_bnb(ctx, res, o_, w_) if DGRAD_BN_STATS else None
+        if part is None:
+            left.append((m_, o_, w_))
+        else:
+            m_.bwd_finalize(ctx, part[0], part[1], w_, M, res.scale, train_bn, invstd, c1, c2, off=o_, ld=part[3], ws_off=part[2])
+    # nothing came with the gradient: ONE pass over the whole tensor; else (a joint conv) one per member with several writers
+    regions = [(0, Ny, left)] if len(left) == len(members) else [(o_, w_, [(m_, o_, w_)]) for m_, o_, w_ in left]
+    for r0, rw, mem in regions:
+        dzs, outs = (dz, out) if rw == Ny else (dz.chan(r0, r0 + rw), out.chan(r0, r0 + rw))
+        rows = ctx.lib.vinet_stats_rows(C.byref(dzs.ct()))
+        ws = ctx.f32(rows * 2 * rw)
+        fsl = L.CAffine(res.scale.data_ptr() + 4 * r0, res.shift.data_ptr() + 4 * r0, 1 if res.relu else 0)
+        ctx.call("vinet_bn_bwd_reduce", C.byref(dzs.ct()), C.byref(outs.ct()), dz.dt, fsl, mean.data_ptr() + 4 * r0,
+                 invstd.data_ptr() + 4 * r0, ws.data_ptr(), ctx.stream, tag=_bn_tag("reduce", rw, dz),
+                 work=dict(flops=0.0, bytes=2 * nb * rw / Ny))
+        for m_, o_, w_ in mem:
+            m_.bwd_finalize(ctx, ws, rows, w_, M, res.scale, train_bn, invstd, c1, c2, off=o_, ld=rw, ws_off=o_ - r0)
+    # A conv whose input needs no gradient (the RGB stem) has one consumer of dz, its weight gradient: kernels
+    # that can form dz from (gradient behind the BN, raw conv output) on the fly spare the apply pass
+    if BN_BWD_FUSE and not x.needs_grad and plan.wants_wgrad() and plan.bias is None and out.dt == dz.dt == ctx.dt:
+        fused = (out, fwd, mean, invstd, c1, c2)
+        q = _wgrad_desc(ctx, plan, x, dz)
+        _set_bnb(q, *fused)
+        if ctx.lib.vinet_conv3d_wgrad_fuses_bn_bwd(C.byref(q)):
+            return dz, fused, None
+    if (SPLIT_IN_APPLY and SPLIT_WGRAD_BF16 and ctx.cdt == F32S and plan.wants_wgrad() and dz.dt == F32 and
+            out.dt == F32 and dz.C % 8 == 0 and dz.ld % 8 == 0 and out.ld % 8 == 0 and ctx.device.type == "cuda"):
+        # fp32s: the hi / lo planes of dy (an operand of the three bf16 weight-gradient launches) leave with the apply pass
+        dh = View.alloc(dz.B, dz.T, dz.H, dz.W, dz.C, BF16, dz.device)
+        dl = View.alloc(dz.B, dz.T, dz.H, dz.W, dz.C, BF16, dz.device)
+        ctx.call("vinet_bn_bwd_apply_split", C.byref(dz.ct()), C.byref(out.ct()), fwd, mean.data_ptr(), invstd.data_ptr(),
+                 c1.data_ptr(), c2.data_ptr(), C.byref(dz.ct()), C.byref(dh.ct()), C.byref(dl.ct()), ctx.stream,
+                 tag=_bn_tag("apply", dz.C, dz), work=dict(flops=0.0, bytes=4 * nb))
+        return dz, None, (dh, dl)
+    ctx.call("vinet_bn_bwd_apply", C.byref(dz.ct()), C.byref(out.ct()), dz.dt, fwd, mean.data_ptr(), invstd.data_ptr(),
+             c1.data_ptr(), c2.data_ptr(), C.byref(dz.ct()), ctx.stream, tag=_bn_tag("apply", dz.C, dz),
+             work=dict(flops=0.0, bytes=3 * nb))
+    return dz, None, None
+
+
+def _bn_tag(what, width, dz):
+    return ("vinet_bn_bwd_%s | C%d x %d voxels" % (what, width, dz.nvox)) if PROFILER is not None else None
+
+
+def _act_backward(ctx, res, act, dz):
+    """stage 1 without a BatchNorm: dz -> dy through the conv's own activation, in the arithmetic's storage type"""
+    if act == L.ACT_RELU and res.grad_masked == res.root().grad_marks and dz.dt == ctx.dt:
+        return dz       # the only writer of dz (the upsample's backward) already gated it with this ReLU
+    if act == L.ACT_NONE and dz.dt == ctx.dt:
+        return dz
+    dy = dz if dz.dt == ctx.dt else View.alloc(dz.B, dz.T, dz.H, dz.W, dz.C, ctx.dt, dz.device)
+    if act != L.ACT_NONE:
+        ctx.call("vinet_act_bwd", C.byref(dz.ct()), dz.dt, C.byref(res.v.ct()), res.v.dt, act, C.byref(dy.ct()), dy.dt, ctx.stream)
+    else:
+        ctx.call("vinet_copy_affine", C.byref(dz.ct()), dz.dt, L.CAffine(None, None, 0), C.byref(dy.ct()), dy.dt, 0, ctx.stream)
+    return dy
+
+
+def _bias_grad(ctx, plan, dy):
+    """stage 2: the conv's bias gradient, a channel sum of dy"""
+    Ny = dy.C
+    rows = ctx.lib.vinet_stats_rows(C.byref(dy.ct()))
+    ws = ctx.f32(rows * 2 * Ny)
+    gb = _param_grad(plan.bias)
+    # channel-padded head: pad-channel gradients are exactly zero, so folding
+    # channels modulo N leaves the real sums untouched
+    assert Ny % plan.N == 0 and (Ny == plan.N or plan.N == 1)
+    ctx.call("vinet_channel_sum", C.byref(dy.ct()), dy.dt, ws.data_ptr(), plan.N, gb.data_ptr(), 1, ctx.stream)
+    _note_param_grad(ctx, plan.bias)
+
+
+class _WgradJob:
+    """stage 3: one conv's weight gradient, ready to run on a weight-gradient stream -- now or later (_schedule_wgrad)"""
+    __slots__ = ("ctx", "plan", "x", "dy", "M", "bn_free", "fused_bnb", "dy_planes", "want_planes")
+
+    def __init__(self, ctx, plan, x, dy, M, bn_free, fused_bnb, dy_planes):
+        self.ctx, self.plan, self.x, self.dy, self.M, self.bn_free = ctx, plan, x, dy, M, bn_free
+        self.fused_bnb, self.dy_planes = fused_bnb, dy_planes       # what stage 1 left: _bn_backward
         # fp32s: hi / lo planes of both operands for the three bf16 launches -- any conv with whole 8-channel groups, and the
         # folded RGB stem (the row-streaming strip kernel, wgrad_hs.hip, over planes of the padded clip)
-        want_planes = bool(SPLIT_WGRAD_BF16 and ctx.cdt == F32S and fused_bnb is None and dy.C % 8 == 0 and x.v.dt == F32 and dy.dt == F32 and
-                           ((not plan.stem and x.fold is None and x.v.C % 8 == 0) or
-                            (plan.stem and x.fold is not None and x.scale is None and x.v.off == 0)))
-        planes_main = None
+        self.want_planes = bool(SPLIT_WGRAD_BF16 and ctx.cdt == F32S and fused_bnb is None and dy.C % 8 == 0 and x.v.dt == F32 and dy.dt == F32 and
+                                ((not plan.stem and x.fold is None and x.v.C % 8 == 0) or
+                                 (plan.stem and x.fold is not None and x.scale is None and x.v.off == 0)))
 
-        def wgrad_job():
-            ctx._side_rr = (getattr(ctx, "_side_rr", -1) + 1) % N_SIDE_STREAMS
-            side = ctx.side_stream(ctx._side_rr)
-            main_ptr = ctx.stream
+    def __call__(self):
+        ctx = self.ctx
+        ctx._side_rr = (ctx._side_rr + 1) % N_SIDE_STREAMS
+        side = ctx.side_stream(ctx._side_rr)
+        if side is not None:
+            if not ctx._joined:
+                side.wait_stream(torch.cuda.current_stream(ctx.device))   # dy (and everything before it) is ready
+            ctx.side_used = True
+        with ctx.on_stream(side, fork=False):
+            self._launch(side)
+        _note_param_grad(ctx, *self.plan.grad_targets())
+
+    def _launch(self, side):
+        ctx, plan, x, dy, M, fused_bnb = self.ctx, self.plan, self.x, self.dy, self.M, self.fused_bnb
+        Ny = dy.C
+        kp = plan.kp(False)
+        nsl = 7 if plan.stem else plan.ntaps
+        # persistent workspace, handed back zeroed by the unpack kernel
+        # (a channel-padded head -- rows past plan.N are never unpacked, so whatever accumulates there over the steps is
+        #  never read -- keeps a persistent workspace too: no allocation and no fill on the weight-gradient stream)
+        persistent = bool(PERSISTENT_DW)
+        dw = plan.dw_workspace(ctx, nsl * Ny * kp) if persistent else ctx.f32(nsl * Ny * kp, zero=True)
+        if persistent:
+            ctx._dw_plans.append(plan)
+        if persistent and any(j[0] == dw.data_ptr() for j in ctx._unpack_jobs):
+            # this plan already ran in this backward (a module used twice in one forward): its workspace holds the
+            # first use's gradient, and the kernels may STORE their result (no split-K, no atomics: "dw is zero on
+            # entry").  Hand that gradient over and get the workspace back zeroed first.
+            plan.unpack_wgrad(ctx, dw, clear=True)
+        wd = _wgrad_desc(ctx, plan, x, dy, dw)
+        if fused_bnb is not None:
+            _set_bnb(wd, *fused_bnb)
+        # the LAST node of the tape (the RGB stem: its input needs no gradient, so nothing of the main stream is
+        # left beside its weight gradient) may take the whole chip; any other conv without a data gradient (the first
+        # SoundNet layer) still has main-stream work beside it and keeps the cap
+        tail = TAIL_WGRAD_FULL and side is not None and not x.needs_grad and ctx._tape_left <= 1
+        wd.max_cus = 256 if (tail or side is None) else (WGRAD_CUS_DEC if self.bn_free else WGRAD_CUS)
+        if DBG_SPIN_SIDE and side is not None:
+            ctx.lib.vinet_debug_spin(DBG_SPIN_SIDE, ctx.stream)
+        if self.want_planes:
+            # the split-bf16 weight gradient as THREE launches of the bf16 kernels (the row- / frame-streaming ones
+            # included) over hi / lo planes of both operands: dw += dy_hi x_hi + dy_lo x_hi + dy_hi x_lo.  Every bf16
+            # weight-gradient kernel adds into dw; the pending affine of x went into its planes.
+            (xh, xl), (dh, dl) = _split_planes(ctx, x, dy, self.dy_planes)
+            for xa, da in ((xh, dl), (xl, dh), (xh, dh)):      # small terms first
+                wq = _wgrad_desc(ctx, plan, xa if isinstance(xa, Act) else Act(xa), da, dw)
+                wq.dtype, wq.max_cus = BF16, wd.max_cus
+                tag, work = _conv_prof(ctx, wq, "wgrad(split x3)", plan, x.v, M, 2, 2, 4)
+                work["flops"] /= 3
+                ctx.call("vinet_conv3d_wgrad", C.byref(wq), ctx.stream, tag=tag, work=work)
             if side is not None:
-                if not getattr(ctx, "_joined", False):
-                    side.wait_stream(torch.cuda.current_stream(ctx.device))   # dy (and everything before it) is ready
-                ctx.side_used = True
-            with (torch.cuda.stream(side) if side is not None else _NullCtx()):
-                if side is not None:
-                    ctx.stream = side.cuda_stream
-                try:
-                    kp = plan.kp(False)
-                    nsl = 7 if plan.stem else plan.ntaps
-                    # persistent workspace, handed back zeroed by the unpack kernel
-                    # (a channel-padded head -- rows past plan.N are never unpacked, so whatever accumulates there over the steps is
-                    #  never read -- keeps a persistent workspace too: no allocation and no fill on the weight-gradient stream)
-                    persistent = bool(PERSISTENT_DW)
-                    dw = plan.dw_workspace(ctx, nsl * Ny * kp) if persistent else ctx.f32(nsl * Ny * kp, zero=True)
-                    if persistent:
-                        ctx._dw_plans.append(plan)
-                    if persistent and any(j[0] == dw.data_ptr() for j in ctx._unpack_jobs):
-                        # this plan already ran in this backward (a module used twice in one forward): its workspace holds the
-                        # first use's gradient, and the kernels may STORE their result (no split-K, no atomics: "dw is zero on
-                        # entry").  Hand that gradient over and get the workspace back zeroed first.
-                        plan.unpack_wgrad(ctx, dw, clear=True)
-                    wd = _wgrad_desc(ctx, plan, x, dy, dw)
-                    if fused_bnb is not None:
-                        zv, zf, zm, zi, z1, z2 = fused_bnb
-                        wd.bnb_z, wd.bnb_ld, wd.bnb_sB, wd.bnb_fwd = zv.ptr(), zv.ld, zv.sB, zf
-                        wd.bnb_mean, wd.bnb_invstd, wd.bnb_c1, wd.bnb_c2 = zm.data_ptr(), zi.data_ptr(), z1.data_ptr(), z2.data_ptr()
-                    es = ESIZE[ctx.dt]
-                    # the LAST node of the tape (the RGB stem: its input needs no gradient, so nothing of the main stream is
-                    # left beside its weight gradient) may take the whole chip; any other conv without a data gradient (the first
-                    # SoundNet layer) still has main-stream work beside it and keeps the cap
-                    tail = TAIL_WGRAD_FULL and side is not None and not x.needs_grad and getattr(ctx, "_tape_left", 0) <= 1
-                    wd.max_cus = 256 if (tail or side is None) else (WGRAD_CUS_DEC if bn is None else WGRAD_CUS)
-                    if DBG_SPIN_SIDE and side is not None:
-                        ctx.lib.vinet_debug_spin(DBG_SPIN_SIDE, ctx.stream)
-                    planes = planes_main
-                    if planes is None and want_planes:
-                        planes = _split_planes(ctx, x, dy, dy_planes)
-                    if planes is not None:
-                        # the split-bf16 weight gradient as THREE launches of the bf16 kernels (the row- / frame-streaming ones
-                        # included) over hi / lo planes of both operands: dw += dy_hi x_hi + dy_lo x_hi + dy_hi x_lo.  Every bf16
-                        # weight-gradient kernel adds into dw; the pending affine of x went into its planes.
-                        (xh, xl), (dh, dl) = planes
-                        for xa, da in ((xh, dl), (xl, dh), (xh, dh)):      # small terms first
-                            wq = _wgrad_desc(ctx, plan, xa if isinstance(xa, Act) else Act(xa), da, dw)
-                            wq.dtype, wq.max_cus = BF16, wd.max_cus
-                            ctx.call("vinet_conv3d_wgrad", C.byref(wq), ctx.stream,
-                                     tag=(_wgrad_kernel_name(ctx, wq) + " | wgrad(split x3) " + plan.site(x.v)) if PROFILER is not None else None,
-                                     work=dict(flops=2.0 * M * plan.N * plan.Cin * plan.ntaps / 3,
-                                               bytes=float(x.v.nvox * plan.Cin * 2 + M * plan.N * 2 + plan.N * plan.Cin * plan.ntaps * 4)))
-                        if side is not None:
-                            ctx.keep(*((p.v if isinstance(p, Act) else p).buf for p in (xh, xl, dh, dl)))
-                    else:
-                        ctx.call("vinet_conv3d_wgrad", C.byref(wd), ctx.stream,
-                                 tag=(_wgrad_kernel_name(ctx, wd) + " | wgrad " + plan.site(x.v)) if PROFILER is not None else None,
-                                 work=dict(flops=2.0 * M * plan.N * plan.Cin * plan.ntaps,
-                                           bytes=float(x.v.nvox * plan.Cin * es + M * plan.N * es + plan.N * plan.Cin * plan.ntaps * 4)))
-                    if Ny != plan.N:
-                        assert plan.ntaps == 1, "channel-padded outputs are only supported for 1x1x1 convs"
-                    if persistent and MULTI_UNPACK and PARAM_GRAD_HOOK is None and N_SIDE_STREAMS == 1:
-                        ctx._unpack_jobs.extend(plan.unpack_jobs(dw))      # one launch for all of them at the end of backward
-                    else:
-                        plan.unpack_wgrad(ctx, dw, clear=persistent)
-                    if side is not None:
-                        ctx.keep(dw, dy.buf, x.v.buf, x.scale, x.shift, *(fused_bnb[2:] if fused_bnb is not None else ()))
-                finally:
-                    ctx.stream = main_ptr
-            _note_param_grad(ctx, *plan.grad_targets())
-
-        # The decoder's weight gradients (convs without BatchNorm: MFMA-bound, persistent, LDS-heavy) would run beside the
-        # decoder's data gradients, which are MFMA-bound too: both lose.  Deferred, they start when the tape reaches the
-        # encoder, whose BN-backward passes and pools are HBM-bound and share a CU with them at little cost.  dy and x
-        # stay untouched meanwhile: gradient buffers are written once per backward and live until the tape is dropped.
-        # (Under stream capture too: the wrong encoder gradients of round 3's captured step came from the per-job joins of the
-        # flush -- a fan-out of redundant graph edges that ROCm 7.2 replays wrongly, see Ctx.flush_deferred -- not from the
-        # deferral; with one join per batch the captured step follows the eager trajectory.)
-        defer = DEFER_DECODER_WGRAD_F32S if ctx.cdt == F32S else DEFER_DECODER_WGRAD
-        group = WGRAD_GROUP_CAPTURE if ctx.capturing else WGRAD_GROUP
-        if defer and bn is None and ctx.side_stream() is not None:
-            ctx._deferred.append(wgrad_job)
-        elif group > 1 and ctx.side_stream() is not None:
-            # weight-gradient jobs leave for their stream `group` at a time behind one join (fewer fork points: every join is an
-            # event pair on the host and, in a replayed graph, ~12 us of cross-queue latency on the main stream's next kernel)
-            ctx._deferred.append(wgrad_job)
-            if len(ctx._deferred) >= group:
-                ctx.flush_deferred()
+                ctx.keep(*((p.v if isinstance(p, Act) else p).buf for p in (xh, xl, dh, dl)))
         else:
+            tag, work = _conv_prof(ctx, wd, "wgrad", plan, x.v, M, ESIZE[ctx.dt], ESIZE[ctx.dt], 4)
+            ctx.call("vinet_conv3d_wgrad", C.byref(wd), ctx.stream, tag=tag, work=work)
+        if Ny != plan.N:
+            assert plan.ntaps == 1, "channel-padded outputs are only supported for 1x1x1 convs"
+        if persistent and MULTI_UNPACK and PARAM_GRAD_HOOK is None and N_SIDE_STREAMS == 1:
+            ctx._unpack_jobs.extend(plan.unpack_jobs(dw))      # one launch for all of them at the end of backward
+        else:
+            plan.unpack_wgrad(ctx, dw, clear=persistent)
+        if side is not None:
+            ctx.keep(dw, dy.buf, x.v.buf, x.scale, x.shift, *(fused_bnb[2:] if fused_bnb is not None else ()))
+
+
+def _schedule_wgrad(ctx, job):
+    """stage 3, WHEN a weight-gradient job leaves for its stream: now, with the next group, or once the tape is in the encoder"""
+    # The decoder's weight gradients (convs without BatchNorm: MFMA-bound, persistent, LDS-heavy) would run beside the
+    # decoder's data gradients, which are MFMA-bound too: both lose.  Deferred, they start when the tape reaches the
+    # encoder, whose BN-backward passes and pools are HBM-bound and share a CU with them at little cost.  dy and x
+    # stay untouched meanwhile: gradient buffers are written once per backward and live until the tape is dropped.
+    # (Under stream capture too: the wrong encoder gradients of round 3's captured step came from the per-job joins of the
+    # flush -- a fan-out of redundant graph edges that ROCm 7.2 replays wrongly, see Ctx.flush_deferred -- not from the
+    # deferral; with one join per batch the captured step follows the eager trajectory.)
+    defer = DEFER_DECODER_WGRAD_F32S if ctx.cdt == F32S else DEFER_DECODER_WGRAD
+    group = WGRAD_GROUP_CAPTURE if ctx.capturing else WGRAD_GROUP
+    if defer and job.bn_free and ctx.side_stream() is not None:
+        ctx._deferred.append(job)
+    elif group > 1 and ctx.side_stream() is not None:
+        # weight-gradient jobs leave for their stream `group` at a time behind one join (fewer fork points: every join is an
+        # event pair on the host and, in a replayed graph, ~12 us of cross-queue latency on the main stream's next kernel)
+        ctx._deferred.append(job)
+        if len(ctx._deferred) >= group:
             ctx.flush_deferred()
-            wgrad_job()
-    # ---- data gradient -------------------------------------------------------------
-    if x.needs_grad:
-        xv = x.v
-        if DBG_SPIN_MAIN and ctx.device.type == "cuda":
-            ctx.lib.vinet_debug_spin(DBG_SPIN_MAIN, ctx.stream)
-        phases, full = plan.dgrad_phases((xv.T, xv.H, xv.W), (out.T, out.H, out.W), ctx.device)
-        ready = x.is_grad_ready()
-        dx = x.grad_view(zero=(not ready and not full))
-        acc = 1 if x.is_grad_ready() else 0
-        wt = plan.packed(ctx, True)
-        if plan.temporal and plan.s[0] > 1 and len(phases) > 1:
-            # all stride phases of a temporal data gradient in one launch where the library has a kernel for it
-            # (dy is read once instead of once per phase): include/vinet_hip.h, tline == 3
-            d = L.CConvDesc()
-            d.dtype, d.out_dtype, d.mode = ctx.cdt, dx.dt, L.CONV_GENERIC
-            d.x, d.y = dy.ct(), dx.ct()
-            d.oT, d.oH, d.oW = xv.T, xv.H, xv.W
-            d.sT, d.sH, d.sW = plan.s[0], 1, 1
-            d.omT = d.omH = d.omW = 1
-            d.ooT = d.ooH = d.ooW = 0
-            d.ntaps, d.taps, d.w, d.Kp = plan.k[0], None, wt.data_ptr(), plan.kp(True)
-            d.pre = L.CAffine(None, None, 0)
-            d.out_scale = d.out_shift = None
-            d.act, d.accumulate, d.stats = L.ACT_NONE, acc, None
-            d.n_valid = plan.Cin if xv.C != plan.Cin else 0
-            d.tline, d.tpad = 3, plan.p[0]
-            if ctx.lib.vinet_conv3d_fuses_dgrad_phases(C.byref(d)):
-                es = ESIZE[ctx.dt]
-                bnb_ws = None
-                if (DGRAD_BN_STATS and not acc and x.mean is not None and x.scale is not None and x.parent is None and
-                        x.fold is None and xv.dt == dx.dt and xv.C == plan.Cin and dx.same_dims(xv)):
-                    # x = relu(bn(z)), this launch is the first (for the stem: the only) writer of its gradient: the partial
-                    # sums of that BatchNorm's backward reduce pass leave with the gradient
-                    d.bnb_z, d.bnb_ld, d.bnb_sB, d.bnb_fwd = xv.ptr(), xv.ld, xv.sB, x.affine()
-                    d.bnb_mean, d.bnb_invstd = x.mean.data_ptr(), x.invstd.data_ptr()
-                    brows = ctx.lib.vinet_conv3d_bn_bwd_stats_rows(C.byref(d))
-                    if brows > 0:
-                        bnb_ws = ctx.f32(brows * 2 * xv.C)
-                        d.bnb_partials = bnb_ws.data_ptr()
-                ctx.call("vinet_conv3d", C.byref(d), ctx.stream,
-                         tag=("conv_tsd_kernel | dgrad " + plan.site(xv)) if PROFILER is not None else None,
-                         work=dict(flops=2.0 * M * plan.N * plan.Cin * plan.ntaps,
-                                   bytes=float(xv.nvox * plan.Cin * es + M * plan.N * es + plan.N * plan.Cin * plan.ntaps * es)))
-                phases = []
-                if bnb_ws is not None:
-                    x.mark_grad_ready()
-                    _register_bnb(ctx, x, bnb_ws, brows)
-                    return
-        # The BatchNorm(s) behind x's pending affine (x itself, or the pending activation it materialises): when this launch is
-        # the LAST writer of x's gradient -- every consumer recorded in forward but this one has written -- and covers it in one
-        # launch, it also writes the partial sums of their backward reduce pass (VinetConvDesc::bnb_*, the shared conv epilogue)
-        bx = x.alias_of if x.alias_of is not None else x
-        bnb_ws, brows = None, 0
-        want_bnb = (DGRAD_BN_STATS >= 2 and len(phases) == 1 and full and bx.mean is not None and bx.scale is not None and bx.relu
-                    and bx.fold is None and ctx.cdt == BF16 and dx.dt == BF16 and bx.v.dt == BF16 and xv.C == plan.Cin
-                    and dx.same_dims(bx.v) and x.root().grad_marks + 1 == x.root().n_readers)
-        for ph in phases:
-            d = L.CConvDesc()
-            d.dtype, d.out_dtype, d.mode = ctx.cdt, dx.dt, L.CONV_GENERIC
-            d.x, d.y = dy.ct(), dx.ct()
-            d.oT, d.oH, d.oW = ph["Q"]
-            d.sT = d.sH = d.sW = 1
-            d.omT, d.omH, d.omW = plan.s
-            d.ooT, d.ooH, d.ooW = ph["r"]
-            d.ntaps, d.taps, d.w, d.Kp = ph["ntaps"], ph["taps"].data_ptr(), wt.data_ptr(), plan.kp(True)
-            d.pre = L.CAffine(None, None, 0)
-            d.out_scale = d.out_shift = None
-            d.act, d.accumulate, d.stats = L.ACT_NONE, acc, None
-            d.n_valid = plan.Cin if xv.C != plan.Cin else 0
-            d.tline, d.tpad = ph["tline"], ph["tpad"]
-            if want_bnb:
-                zv = bx.v
-                d.bnb_z, d.bnb_ld, d.bnb_sB, d.bnb_fwd = zv.ptr(), zv.ld, zv.sB, bx.affine()
-                d.bnb_mean, d.bnb_invstd = bx.mean.data_ptr(), bx.invstd.data_ptr()
-                brows = ctx.lib.vinet_conv3d_bn_bwd_stats_rows(C.byref(d))
-                if brows > 0:
-                    bnb_ws = ctx.f32(brows * 2 * zv.C)
-                    d.bnb_partials = bnb_ws.data_ptr()
-            es = ESIZE[ctx.dt]
-            nph = len(phases)
-            ctx.call("vinet_conv3d", C.byref(d), ctx.stream,
-                     tag=(_conv_kernel_name(ctx, d) + ("+bnb" if bnb_ws is not None else "") + " | dgrad " + plan.site(xv)) if PROFILER is not None else None,
-                     work=dict(flops=2.0 * M * plan.N * plan.Cin * plan.ntaps / nph,
-                               bytes=float(xv.nvox * plan.Cin * es + M * plan.N * es + plan.N * plan.Cin * plan.ntaps * es) / nph))
-        x.mark_grad_ready()
-        if bnb_ws is not None:
-            _register_bnb(ctx, bx, bnb_ws, brows)
+    else:
+        ctx.flush_deferred()
+        job()
+
+
+def _bnb_partials(ctx, d, a):
+    """the data gradient `d`, which writes the gradient of `a` = relu(bn(z)), also leaves the partial sums of that BatchNorm's
+    backward reduce pass: (partials, rows) for _register_bnb, or None if the library's kernel for `d` cannot"""
+    _set_bnb(d, a.v, a.affine(), a.mean, a.invstd)
+    rows = ctx.lib.vinet_conv3d_bn_bwd_stats_rows(C.byref(d))
+    if rows <= 0:
+        return None
+    ws = ctx.f32(rows * 2 * a.v.C)
+    d.bnb_partials = ws.data_ptr()
+    return ws, rows
+
+
+def _data_grad(ctx, plan, x, out, dy, M):
+    """stage 4: dx, as ONE launch over all stride phases where the library has a kernel for it, else one launch per phase"""
+    xv = x.v
+    if DBG_SPIN_MAIN and ctx.device.type == "cuda":
+        ctx.lib.vinet_debug_spin(DBG_SPIN_MAIN, ctx.stream)
+    phases, full = plan.dgrad_phases((xv.T, xv.H, xv.W), (out.T, out.H, out.W), ctx.device)
+    dx = x.grad_view(zero=not (full or x.is_grad_ready()))
+    acc = 1 if x.is_grad_ready() else 0          # (a gradient just allocated zero-filled counts as written)
+    wt = plan.packed(ctx, True)
+    n_valid = plan.Cin if xv.C != plan.Cin else 0
+    es = ESIZE[ctx.dt]
+    if plan.temporal and plan.s[0] > 1 and len(phases) > 1:
+        # all stride phases of a temporal data gradient in one launch where the library has a kernel for it
+        # (dy is read once instead of once per phase): include/vinet_hip.h, tline == 3
+        d = _conv_desc(ctx, L.CONV_GENERIC, dy, dx, (xv.T, xv.H, xv.W), (plan.s[0], 1, 1), (1, 1, 1), (0, 0, 0), plan.k[0], None,
+                       wt, plan.kp(True), L.CAffine(None, None, 0), n_valid, plan.promise("dgrad_fused"), acc)
+        if ctx.lib.vinet_conv3d_fuses_dgrad_phases(C.byref(d)):
+            part = None
+            if (DGRAD_BN_STATS and not acc and x.mean is not None and x.scale is not None and x.parent is None and
+                    x.fold is None and xv.dt == dx.dt and xv.C == plan.Cin and dx.same_dims(xv)):
+                # x = relu(bn(z)), this launch is the first (for the stem: the only) writer of its gradient: the partial
+                # sums of that BatchNorm's backward reduce pass leave with the gradient
+                part = _bnb_partials(ctx, d, x)
+            tag, work = _conv_prof(ctx, "conv_tsd_kernel", "dgrad", plan, xv, M, es, es, es)
+            ctx.call("vinet_conv3d", C.byref(d), ctx.stream, tag=tag, work=work)
+            x.mark_grad_ready()
+            if part is not None:
+                _register_bnb(ctx, x, *part)
+            return
+    # The BatchNorm(s) behind x's pending affine (x itself, or the pending activation it materialises): when this launch is
+    # the LAST writer of x's gradient -- every consumer recorded in forward but this one has written -- and covers it in one
+    # launch, it also writes the partial sums of their backward reduce pass (VinetConvDesc::bnb_*, the shared conv epilogue)
+    bx = x.alias_of if x.alias_of is not None else x
+    want_bnb = (DGRAD_BN_STATS >= 2 and len(phases) == 1 and full and bx.mean is not None and bx.scale is not None and bx.relu
+                and bx.fold is None and ctx.cdt == BF16 and dx.dt == BF16 and bx.v.dt == BF16 and xv.C == plan.Cin
+                and dx.same_dims(bx.v) and x.root().grad_marks + 1 == x.root().n_readers)
+    part = None
+    for ph in phases:
+        d = _conv_desc(ctx, L.CONV_GENERIC, dy, dx, ph["Q"], (1, 1, 1), plan.s, ph["r"], ph["ntaps"], ph["taps"], wt, plan.kp(True),
+                       L.CAffine(None, None, 0), n_valid, ph["promise"], acc)
+        if want_bnb:
+            part = _bnb_partials(ctx, d, bx)
+        tag, work = _conv_prof(ctx, d, "dgrad", plan, xv, M, es, es, es, len(phases), "+bnb" if part is not None else "")
+        ctx.call("vinet_conv3d", C.byref(d), ctx.stream, tag=tag, work=work)
+    x.mark_grad_ready()
+    if part is not None:
+        _register_bnb(ctx, bx, *part)
 
 
 # ----------------------------------------------------------------------------

@@ -249,14 +249,14 @@ class _Mixed(_Block):
         def m_enter(k):
             def f():
                 if not ctx.capturing:
-                    ctx._bwd_cm = ctx.on_stream(fork[k])
-                    ctx._bwd_cm.__enter__()
+                    ctx.bwd_cm = ctx.on_stream(fork[k])
+                    ctx.bwd_cm.__enter__()
             return f
 
         def m_exit():
             if not ctx.capturing:
-                ctx._bwd_cm.__exit__(None, None, None)
-                ctx._bwd_cm = None
+                ctx.bwd_cm.__exit__(None, None, None)
+                ctx.bwd_cm = None
 
         def m_join():
             if not ctx.capturing:
