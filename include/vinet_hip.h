@@ -445,17 +445,67 @@ int vinet_gt_preprocess(const uint8_t* src, int32_t N, int32_t H, int32_t W, flo
                         void* stream);
 
 /* misc */
-/* Tuning / A-B switches (process-wide): "dma" (1 = use the LDS-DMA conv kernel where
- * legal, default 1), "wgrad_tr" (1 = hardware transpose reads in the register-staged wgrad, default 1),
- * "wgrad_dma" (1 = LDS-DMA multi-tap wgrad kernel where legal, default 1),
- * "pp" (256x256x64 / 256x192x64 ping-pong conv kernel: 0 off, 1 heuristic (default), 2 force, 3 / 4 force the
- * 256- / 192-wide shape), "wgrad_pp" (ping-pong wgrad kernel, same values; 3 / 4 force the 256- / 192-row tile),
- * "wgrad_tg" (taps per group of the 64x64 wgrad kernel, 0 = heuristic), "pool_twalk" (T-walking 3x3x3/s1 pool
- * kernels: 0 off, 1 large tensors (default), 2 always), "tperm" (t-fastest tile order, default 0),
- * "n64_tile" (64-wide convs: 0 heuristic, 1 force 128-row, 2 force 64-row tiles),
- * "conv_ts" / "conv_hs" / "wgrad_ts" / "wgrad_hs" / "wgrad_rs" / "wgrad_tf" (streaming kernels: 0 off, 1 heuristic
- * (default), 2 every eligible shape), "reduce_il" (channel reductions walk one window, default 1).
- * None of them changes results beyond floating-point accumulation order. */
+/* Tuning / A-B switches (process-wide), `name` (default): meaning.  The list is vinet_amd/csrc/options.h, the one table the
+ * library defines its switches from.  None of them changes results beyond floating-point accumulation order.
+ * Returns 0; -1 for an unknown name; -2 for a value that needs a -DVINET_EXPERIMENTS build of the library.
+ *   "dma" (1): LDS-DMA conv kernel (conv_dma) where legal; 0 = the register-staged kernel
+ *   "dma3" (1): LDS-DMA kernel for the split-bf16 form (conv_dma3); 0 = the register-staged kernel
+ *   "pp" (1): 256x256x64 ping-pong conv kernel: 0 off, 1 heuristic, 2 force, 3 / 4 force the 256- / 192-wide shape
+ *   "pp_pw_kt" (8): ping-pong kernel on pointwise layers from this many K tiles of 64 (16 = as for every other layer)
+ *   "pw" (1): pointwise streaming kernel (conv_pw) for 1x1x1 convs and their data gradients: 0 off, 1 heuristic, 2 also on
+ *       small grids (tests)
+ *   "pw_maxtn" (4): pointwise kernel: at most this many column tiles (each re-reads x)
+ *   "ht" (1): halo-tile conv kernels (conv_ht): 0 off, 1 heuristic, 2 every eligible conv (tests)
+ *   "ht3" (1): halo-tile kernels for the split-bf16 form; 0 = conv_dma3 everywhere
+ *   "ht_minhw" (1344): halo tiles, spatial mode: smallest H x W the heuristic takes
+ *   "ht_t" (1): temporal mode of the halo-tile kernel for (3,1,1) / stride-1 convs; 0 off
+ *   "ht_t_minhw" (336): halo tiles, temporal mode: smallest H x W the heuristic takes
+ *   "ht_pre" (0): halo tiles, spatial mode, on inputs with a pending BatchNorm + ReLU: 1 on
+ *   "conv_hs" (1): strip-streaming kernel of the folded stem (conv_hs): 0 off, 1 heuristic, 2 every eligible shape (tests)
+ *   "conv_hs_segs" (1): conv_hs: row segments for launches on small grids; 0 = whole strips only
+ *   "conv_ts" (1): frame-streaming temporal 64 -> 64 kernels (conv_ts, conv_tsd): 0 off, 1 heuristic, 2 every eligible
+ *       shape (tests)
+ *   "conv_ts_segs" (1): conv_ts: frame segments for launches on small grids; 0 = whole patches only
+ *   "splitk" (1): split-K on grids that cannot fill the chip: 0 off, 1 on, n >= 2 = minimum K chunks (of 32) per split
+ *   "sk_tile" (7): tiles of long-K small-grid convs whose caller lends split-K scratch: bit 0 128x192, bit 1 128x128, bit
+ *       2 / 3 128x64 / 256x64
+ *   "n64_tile" (0): tuning: 64-wide layers on 128x64 (1) or 64x64 (2) tiles instead of 256x64
+ *   "n64_kmax" (64): 64-wide outputs: 128-row tiles up to this many K steps of 32 (0 = never)
+ *   "n128_tile" (0): tuning: 128-wide layers on 128x128 (1) or 64x128 (2) tiles instead of 256x128
+ *   "n128_kmax" (64): 128-wide outputs: 128-row tiles up to this many K steps of 32 (0 = never)
+ *   "n192_tile" (1): 128x192 tiles for N % 192 == 0 instead of 256x96: 0 off, 1 heuristic, 2 also on small grids (tests)
+ *   "tperm" (0): t-fastest M-tile order (L2 reuse across temporal taps): 1 on
+ *   "epi_rows" (0): conv epilogue stores whole rows through a wave-private LDS image: 1 on (-DVINET_EXPERIMENTS builds
+ *       only)
+ *   "bnb_epi" (1): BatchNorm-backward partial sums out of the shared conv epilogue; 0 = only the fused temporal data
+ *       gradient
+ *   "wgrad_dma" (1): LDS-DMA multi-tap weight-gradient kernel where legal; 0 = the register-staged kernel
+ *   "wgrad_tg" (0): tuning: taps per group in the LDS-DMA weight gradient (0 = heuristic)
+ *   "wgrad_tr" (1): hardware transpose reads in the register-staged weight gradient; 0 = scalar LDS reads
+ *   "wgrad_pp" (1): 256x256x64 ping-pong weight gradient: 0 off, 1 heuristic, 2 force, 3 / 4 force the 256- / 192-row tile
+ *   "wgrad_pp_cap" (1): the ping-pong weight gradient honours VinetWgradDesc::max_cus; 0 = always the whole chip
+ *   "wgrad_ts" (1): frame-streaming weight gradient of temporal 64 -> 64 convs: 0 off, 1 heuristic, 2 every eligible shape
+ *       (tests)
+ *   "wgrad_ts_cap" (0): the frame-streaming weight gradient honours VinetWgradDesc::max_cus: 1 on
+ *   "wgrad_hs" (1): strip-streaming weight gradient of the folded stem: 0 off, 1 heuristic, 2 every eligible shape (tests)
+ *   "wgrad_rs" (1): row-streaming weight gradient of 1x3x3 convs: 0 off, 1 heuristic, 2 every eligible shape (tests)
+ *   "wgrad_rs4" (1): row-streaming weight gradient: the four-wave form for W = 24, 48, 32, 64, 96; 0 = the eight-wave
+ *       kernels
+ *   "wgrad_tf" (1): temporal-tap weight gradient (wgrad_tf): 0 off, 1 heuristic, 2 every eligible shape (tests)
+ *   "wgrad_skinny" (1): weight gradient of pointwise convs with 8 output channels: 0 off, 1 heuristic, 2 every eligible
+ *       shape (tests)
+ *   "bn_lean" (1): register-lean bf16 BatchNorm-backward kernels: 0 = the generic 8-channel forms, 2 = a
+ *       -DVINET_EXPERIMENTS variant
+ *   "bn_rows" (1024): cap on the workgroups (= partial rows) of a channel reduction (clamped to >= 1)
+ *   "reduce_il" (1): channel reductions: blocks interleave rounds over one window; 0 = one contiguous range per block
+ *   "reduce_small" (1): tensors of <= 64 voxels take channel_reduce_small_kernel; 0 off
+ *   "pack_tiled" (1): LDS-tiled multi-tensor pack / unpack; 0 = the element-wise kernels
+ *   "pool_lds" (1): LDS halo-tile 3x3x3/s1 max-pool forward (C % 64 == 0): 0 off, 1 large tensors, 2 always
+ *   "pool_pk" (1): bf16: packed 32-bit-key form of the LDS halo-tile pool; 0 = the fp32-compare kernel
+ *   "pool_twalk" (1): T-walking 3x3x3/s1 max-pool backward: 0 off, 1 large tensors, 2 always, 3 conditional-load form, 4
+ *       bf16 without the EXEC-mask routing
+ *   "pool_blk" (1): strided max-pool backward per 2x2 input block; 0 off
+ *   "up_blk" (1): 8-channel upsample kernels (forward per 2x2 output block); 0 off */
 int vinet_set_option(const char* name, int32_t value);
 /* fp32 view (with its pending affine applied) -> hi = bf16(v) and lo = bf16(v - hi) planes of the same dims: the operands of
  * the bf16 kernels when they serve the VINET_F32S arithmetic as three accumulating launches (hi*hi + lo*hi + hi*lo; the weight

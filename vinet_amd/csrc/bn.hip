@@ -275,9 +275,7 @@ __global__ __launch_bounds__(256, WPE) void bn_bwd_reduce8_bf16_kernel(TView x, 
     }
   }
 }
-int g_vinet_opt_bn_lean = 1;    // register-lean bf16 BatchNorm-backward kernels (0 = the generic 8-channel forms)
 
-int g_vinet_opt_bn_rows = 1024;  // cap on the workgroups (= partial rows) of a channel reduction
 static inline int stats_rows_for(long nvox) {
   long rows = (nvox + 63) / 64;
   if (rows > g_vinet_opt_bn_rows) rows = g_vinet_opt_bn_rows;
@@ -385,7 +383,6 @@ __global__ __launch_bounds__(64) void channel_reduce_small_kernel(TView x, TView
   partials[x.C + c] = p;
 }
 
-int g_vinet_opt_reduce_small = 1;   // tensors of <= 64 voxels take channel_reduce_small_kernel
 template <int MODE>
 static int launch_channel_reduce(const VinetTensor* x, const VinetTensor* dz, int dtype, VinetAffine fwd,
                                  const float* mean, const float* invstd, float* partials, void* stream) {

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "vinet_hip.h"
+#include "options.h"
 
 typedef uint16_t bf16_t;  // storage type; arithmetic is always fp32
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_v;

@@ -11,7 +11,7 @@
 //   * per output row: scale / shift / activation, BN partial sums (one `stats` row per 64 positions), bf16 tile
 //     through LDS, 16-byte coalesced stores;
 //   * the padded image makes every access in range: no bounds checks.
-#include "common.h"
+#include "conv_host.h"
 
 struct ConvHsArgs {
   const char* x;
@@ -199,7 +199,6 @@ __global__ __launch_bounds__(256, 2) void conv_hs_kernel(const ConvHsArgs a) {
   }
 }
 
-
 // ---- the same strip kernel in the split-bf16 form (VINET_F32S): fp32 folded clip, fp32 output, hi / lo weight planes ------------
 // A position of the overlapped view is 8 fp32 pixels-x-channels = 32 bytes (position v starts 32 bytes after position v - 1); the K
 // order inside a 32-wide chunk is the one vinet_pack_weights(VINET_F32S) gives the weight planes (conv_dma3.h): lane group q holds
@@ -368,9 +367,6 @@ __global__ __launch_bounds__(256, 2) void conv_hs3_kernel(const ConvHsArgs a) {
     }
   }
 }
-
-int g_vinet_opt_conv_hs = 1;   // 0 = off, 2 = force on every eligible shape (tests)
-int g_vinet_opt_conv_hs_segs = 1;   // row segments for launches without statistics (0 = whole strips only)
 
 // row segments per strip: enough items for one round of 768 workgroups, at least 7 output rows each (a segment re-reads 5 input
 // rows of its upper neighbour); 1 in the split form.  (Not a function of d->stats: the engine asks vinet_conv3d_stats_rows

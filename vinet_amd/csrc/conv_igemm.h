@@ -14,7 +14,7 @@
 // The same kernel serves forward convs, every dgrad (the caller passes the
 // transposed weight pack and per-phase tap tables) and SoundNet's 1-D convs.
 #pragma once
-#include "common.h"
+#include "conv_host.h"
 
 struct ConvArgs {
   const char* x;
@@ -831,19 +831,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
   conv_epilogue<MT, NT, WARPS_M, WARPS_N>(a, acc, smem, tile_m, tile_n);
 }
 
-// ---- host-side dispatch helpers ---------------------------------------------
-struct ConvTile { int MT, NT, WM, WN; int BM() const { return 16 * MT * WM; } int BN() const { return 16 * NT * WN; } };
-
-// Tile choice is a pure function of (dtype, mode, M, N) so callers can size the
-// statistics workspace (vinet_conv3d_tile_m).
-ConvTile vinet_pick_conv_tile(int dtype, int mode, long M, int N, long kchunks, bool may_split = false);
-int vinet_launch_conv_bf16(const ConvTile& t, int mode, const ConvArgs& a, hipStream_t s);
-int vinet_launch_conv_f32(const ConvTile& t, int mode, const ConvArgs& a, hipStream_t s, bool split = false);
-int vinet_launch_conv_dma_bf16(const ConvTile& t, const ConvArgs& a, hipStream_t s);
-int vinet_launch_conv_pp_bf16(int bn, const ConvArgs& a, hipStream_t s);
-int vinet_launch_conv_ht_bf16(int nt, int tw, int tm, int pre, const ConvArgs& a, hipStream_t s);
-int vinet_launch_conv_pw_bf16(int nt, const ConvArgs& a, hipStream_t s);
-
+// ---- host-side dispatch helpers (ConvTile and the cross-file prototypes: conv_host.h) -----
 template <typename T, int MT, int NT, int WM, int WN, int MODE, bool SPLIT = false>
 static int launch_conv_cfg(const ConvArgs& a, hipStream_t s) {
   using Cfg = ConvCfg<T, MT, NT, WM, WN, SPLIT>;

@@ -16,7 +16,7 @@
 //     vinet_conv3d_tile_m reports 64), bf16 tile through LDS, 16-byte coalesced stores (optional read-modify-write);
 //   * the tap table is read on the device; the host only needs the caller's promise (VinetConvDesc::tline) that the
 //     taps are temporal and their offsets form the contiguous range [-tpad, -tpad + ntaps - 1].
-#include "common.h"
+#include "conv_host.h"
 
 struct ConvTsArgs {
   const char* x;
@@ -285,7 +285,6 @@ __global__ __launch_bounds__(256, 2) void conv_ts_kernel(const ConvTsArgs a) {
   }
 }
 
-
 // ---- the same frame-streaming kernel in the split-bf16 form (VINET_F32S: fp32 x and y, hi / lo weight planes) --------------------
 // The split happens ONCE per loaded element, on the way into the LDS ring (where the pending BatchNorm + ReLU is applied anyway):
 // a frame is kept as a hi and a lo bf16 plane, [32 positions][64 channels] each, with the channels of every 32-wide chunk in the K
@@ -488,9 +487,6 @@ __global__ __launch_bounds__(256, 2) void conv_ts3_kernel(const ConvTsArgs a) {
   }
 }
 
-int g_vinet_opt_conv_ts = 1;   // 0 = off, 2 = force on every eligible shape (tests)
-
-int g_vinet_opt_conv_ts_segs = 1;   // frame segments for launches without statistics (0 = whole patches only)
 // frame segments per patch: enough items for one round of 512 workgroups, at least 4 output frames each (a segment re-reads
 // k - s input frames of its predecessor); 1 in the split form.  (Not a function of d->stats: the engine asks
 // vinet_conv3d_stats_rows before it has a statistics buffer to point at.)

@@ -9,26 +9,7 @@
 // grid = (tilesN * tilesC, ntaps, splitK); workgroup = 4 waves (2x2), each wave
 // a 32x32 block of the 64(n) x 64(c) tile; split-K partials are combined with
 // fp32 atomics into the caller-zeroed dw buffer.
-#include "common.h"
-
-extern int g_vinet_opt_wgrad_tr;
-extern int g_vinet_opt_wgrad_dma;
-extern int g_vinet_opt_wgrad_tg;
-int vinet_launch_wgrad_dma(const VinetWgradDesc* d, hipStream_t s);
-int vinet_wgrad_dma_name(const VinetWgradDesc* d, char* buf, int n);
-bool vinet_wgrad_use_pp(const VinetWgradDesc* d);
-bool vinet_wgrad_use_ts(const VinetWgradDesc* d);
-bool vinet_wgrad_use_hs(const VinetWgradDesc* d);
-bool vinet_wgrad_use_rs(const VinetWgradDesc* d);
-int vinet_launch_wgrad_rs(const VinetWgradDesc* d, hipStream_t s);
-bool vinet_wgrad_use_skinny(const VinetWgradDesc* d);
-int vinet_launch_wgrad_skinny(const VinetWgradDesc* d, hipStream_t s);
-bool vinet_wgrad_use_tf(const VinetWgradDesc* d);
-int vinet_launch_wgrad_tf(const VinetWgradDesc* d, hipStream_t s);
-int vinet_launch_wgrad_hs(const VinetWgradDesc* d, hipStream_t s);
-int vinet_launch_wgrad_ts(const VinetWgradDesc* d, hipStream_t s);
-int vinet_wgrad_pp_rows(int N);
-int vinet_launch_wgrad_pp(const VinetWgradDesc* d, hipStream_t s);
+#include "conv_host.h"
 
 struct WgradArgs {
   const char* x;
@@ -294,43 +275,40 @@ static bool wgrad_use_dma(const VinetWgradDesc* d) {
          !(d->pre.relu && !d->pre.scale);
 }
 
+// the one ladder of the weight gradients, in launch order: the first eligible family takes the problem
+WgradRoute vinet_wgrad_route(const VinetWgradDesc* d) {
+  if (vinet_wgrad_use_skinny(d)) return {WGRAD_SKINNY};
+  if (vinet_wgrad_use_rs(d)) return {WGRAD_RS};
+  if (vinet_wgrad_use_hs(d)) return {WGRAD_HS};
+  if (vinet_wgrad_use_ts(d)) return {WGRAD_TS};
+  if (vinet_wgrad_use_tf(d)) return {WGRAD_TF};
+  if (!wgrad_use_dma(d)) return {WGRAD_GENERIC};
+  return {vinet_wgrad_use_pp(d) ? WGRAD_PP : WGRAD_DMA};
+}
+
 extern "C" int vinet_conv3d_wgrad_kernel_name(const VinetWgradDesc* d, char* buf, int32_t n) {
   if (!d || !buf || n <= 0) return -1;
-  if (vinet_wgrad_use_skinny(d)) { snprintf(buf, n, "wgrad_skinny_kernel"); return 0; }
-  if (vinet_wgrad_use_rs(d)) { snprintf(buf, n, "conv_wgrad_rs_kernel<W%d>", d->dy.W); return 0; }
-  if (vinet_wgrad_use_hs(d)) { snprintf(buf, n, d->bnb_z ? "conv_wgrad_hs_kernel<bn_bwd>" : "conv_wgrad_hs_kernel"); return 0; }
-  if (vinet_wgrad_use_ts(d)) { snprintf(buf, n, "conv_wgrad_ts_kernel<%s>", d->pre.scale ? "pre" : "plain"); return 0; }
-  if (vinet_wgrad_use_tf(d)) { snprintf(buf, n, "conv_wgrad_tf_kernel<%s>", d->pre.scale ? "pre" : "plain"); return 0; }
-  if (wgrad_use_dma(d) && vinet_wgrad_use_pp(d)) { snprintf(buf, n, "conv_wgrad_pp_kernel<%s,%d>", d->pre.scale ? "pre" : "plain", vinet_wgrad_pp_rows(d->dy.C)); return 0; }
-  if (wgrad_use_dma(d)) return vinet_wgrad_dma_name(d, buf, n);
-  snprintf(buf, n, "conv_wgrad_kernel<%s,%d>", d->dtype == VINET_BF16 ? "bf16" : (d->dtype == VINET_F32S ? "float/split" : "float"), d->mode);
+  const char* pre = d->pre.scale ? "pre" : "plain";
+  switch (vinet_wgrad_route(d).kind) {
+    case WGRAD_SKINNY: snprintf(buf, n, "wgrad_skinny_kernel"); break;
+    case WGRAD_RS: snprintf(buf, n, "conv_wgrad_rs_kernel<W%d>", d->dy.W); break;
+    case WGRAD_HS: snprintf(buf, n, d->bnb_z ? "conv_wgrad_hs_kernel<bn_bwd>" : "conv_wgrad_hs_kernel"); break;
+    case WGRAD_TS: snprintf(buf, n, "conv_wgrad_ts_kernel<%s>", pre); break;
+    case WGRAD_TF: snprintf(buf, n, "conv_wgrad_tf_kernel<%s>", pre); break;
+    case WGRAD_PP: snprintf(buf, n, "conv_wgrad_pp_kernel<%s,%d>", pre, vinet_wgrad_pp_rows(d->dy.C)); break;
+    case WGRAD_DMA: return vinet_wgrad_dma_name(d, buf, n);
+    case WGRAD_GENERIC: snprintf(buf, n, "conv_wgrad_kernel<%s,%d>", d->dtype == VINET_BF16 ? "bf16" : (d->dtype == VINET_F32S ? "float/split" : "float"), d->mode); break;
+  }
   return 0;
 }
 
+// (only the strip-streaming kernel of the stem applies the BatchNorm backward; the families ahead of it in the ladder exclude its problems)
 extern "C" int vinet_conv3d_wgrad_fuses_bn_bwd(const VinetWgradDesc* d) {
-  return d && d->bnb_z && vinet_wgrad_use_hs(d) ? 1 : 0;
+  return d && d->bnb_z && vinet_wgrad_route(d).kind == WGRAD_HS ? 1 : 0;
 }
 
-extern "C" int vinet_conv3d_wgrad(const VinetWgradDesc* d, void* stream) {
-  VN_CHECK_ARG(d != nullptr, "wgrad: null descriptor");
-  VN_CHECK_ARG(!d->bnb_z || vinet_conv3d_wgrad_fuses_bn_bwd(d), "wgrad: fused BN backward requested for a problem whose kernel cannot apply it");
-  VN_CHECK_ARG(d->dtype == VINET_F32 || d->dtype == VINET_BF16 || d->dtype == VINET_F32S, "wgrad: bad dtype %d", d->dtype);
-  const int eg = vn_f32_storage(d->dtype) ? 4 : 8;
-  VN_CHECK_ARG(vn_tensor_ok(d->x, d->mode == VINET_CONV_STEM ? 4 : eg, true), "wgrad: bad x view");
-  VN_CHECK_ARG(vn_tensor_ok(d->dy, eg), "wgrad: bad dy view");
-  VN_CHECK_ARG(d->x.B == d->dy.B, "wgrad: batch mismatch");
-  VN_CHECK_ARG(d->ntaps > 0 && d->taps && d->dw, "wgrad: taps/dw missing");
-  VN_CHECK_ARG(d->Kp > 0 && d->Kp % 32 == 0, "wgrad: Kp must be a multiple of 32");
-  if (d->mode == VINET_CONV_STEM) VN_CHECK_ARG(d->x.C == 4 && d->Kp == 32, "wgrad stem: x.C must be 4, Kp 32");
-  else VN_CHECK_ARG(d->Kp >= d->x.C, "wgrad: Kp < Cin");
-
-  if (vinet_wgrad_use_skinny(d)) return vinet_launch_wgrad_skinny(d, (hipStream_t)stream);
-  if (vinet_wgrad_use_rs(d)) return vinet_launch_wgrad_rs(d, (hipStream_t)stream);
-  if (vinet_wgrad_use_hs(d)) return vinet_launch_wgrad_hs(d, (hipStream_t)stream);
-  if (vinet_wgrad_use_ts(d)) return vinet_launch_wgrad_ts(d, (hipStream_t)stream);
-  if (vinet_wgrad_use_tf(d)) return vinet_launch_wgrad_tf(d, (hipStream_t)stream);
-  if (wgrad_use_dma(d) && vinet_wgrad_use_pp(d)) return vinet_launch_wgrad_pp(d, (hipStream_t)stream);
-  if (wgrad_use_dma(d)) return vinet_launch_wgrad_dma(d, (hipStream_t)stream);
+// the register-staged fallback: 64 x 64 tiles per tap, split-K over voxel chunks to ~2048 workgroups
+static int vinet_launch_wgrad_generic(const VinetWgradDesc* d, hipStream_t s) {
   WgradArgs a;
   a.x = (const char*)d->x.ptr; a.dy = (const char*)d->dy.ptr; a.dw = d->dw; a.taps = (const int4*)d->taps;
   a.in_scale = d->pre.scale; a.in_shift = d->pre.shift; a.in_relu = d->pre.relu;
@@ -355,7 +333,6 @@ extern "C" int vinet_conv3d_wgrad(const VinetWgradDesc* d, void* stream) {
   a.dW = make_fastdiv(a.Wo); a.dH = make_fastdiv(a.Ho); a.dT = make_fastdiv(a.To);
 
   dim3 grid(a.tilesN * a.tilesC, a.ntaps, a.splitK);
-  hipStream_t s = (hipStream_t)stream;
   if (d->dtype == VINET_BF16) {
     if (d->mode == VINET_CONV_STEM) hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, VINET_CONV_STEM>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((conv_wgrad_kernel<bf16_t, VINET_CONV_GENERIC>), grid, dim3(256), 0, s, a);
@@ -367,4 +344,31 @@ extern "C" int vinet_conv3d_wgrad(const VinetWgradDesc* d, void* stream) {
     else hipLaunchKernelGGL((conv_wgrad_kernel<float, VINET_CONV_GENERIC>), grid, dim3(256), 0, s, a);
   }
   return vn_launch_status("conv_wgrad");
+}
+
+extern "C" int vinet_conv3d_wgrad(const VinetWgradDesc* d, void* stream) {
+  VN_CHECK_ARG(d != nullptr, "wgrad: null descriptor");
+  const WgradKind kind = vinet_wgrad_route(d).kind;
+  VN_CHECK_ARG(!d->bnb_z || kind == WGRAD_HS, "wgrad: fused BN backward requested for a problem whose kernel cannot apply it");
+  VN_CHECK_ARG(d->dtype == VINET_F32 || d->dtype == VINET_BF16 || d->dtype == VINET_F32S, "wgrad: bad dtype %d", d->dtype);
+  const int eg = vn_f32_storage(d->dtype) ? 4 : 8;
+  VN_CHECK_ARG(vn_tensor_ok(d->x, d->mode == VINET_CONV_STEM ? 4 : eg, true), "wgrad: bad x view");
+  VN_CHECK_ARG(vn_tensor_ok(d->dy, eg), "wgrad: bad dy view");
+  VN_CHECK_ARG(d->x.B == d->dy.B, "wgrad: batch mismatch");
+  VN_CHECK_ARG(d->ntaps > 0 && d->taps && d->dw, "wgrad: taps/dw missing");
+  VN_CHECK_ARG(d->Kp > 0 && d->Kp % 32 == 0, "wgrad: Kp must be a multiple of 32");
+  if (d->mode == VINET_CONV_STEM) VN_CHECK_ARG(d->x.C == 4 && d->Kp == 32, "wgrad stem: x.C must be 4, Kp 32");
+  else VN_CHECK_ARG(d->Kp >= d->x.C, "wgrad: Kp < Cin");
+  hipStream_t s = (hipStream_t)stream;
+  switch (kind) {
+    case WGRAD_SKINNY: return vinet_launch_wgrad_skinny(d, s);
+    case WGRAD_RS: return vinet_launch_wgrad_rs(d, s);
+    case WGRAD_HS: return vinet_launch_wgrad_hs(d, s);
+    case WGRAD_TS: return vinet_launch_wgrad_ts(d, s);
+    case WGRAD_TF: return vinet_launch_wgrad_tf(d, s);
+    case WGRAD_PP: return vinet_launch_wgrad_pp(d, s);
+    case WGRAD_DMA: return vinet_launch_wgrad_dma(d, s);
+    case WGRAD_GENERIC: break;
+  }
+  return vinet_launch_wgrad_generic(d, s);
 }

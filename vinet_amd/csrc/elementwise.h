@@ -5,14 +5,6 @@
 #pragma once
 #include "common.h"
 
-extern int g_vinet_opt_pool_twalk;
-extern int g_vinet_opt_pool_lds;
-extern int g_vinet_opt_pool_pk;
-extern int g_vinet_opt_up_blk;
-extern int g_vinet_opt_reduce_il;
-extern int g_vinet_opt_pool_blk;
-extern int g_vinet_opt_pool_pk;
-
 // ---- 4-channel ("quad") typed access -----------------------------------------
 template <typename T> VN_DEV float4 ldq(const T* p);
 template <> VN_DEV float4 ldq<float>(const float* p) { return *(const float4*)p; }

@@ -1,6 +1,7 @@
 // Layout and packing kernels: conv weights -> packed bf16 / fp32 tiles (single and multi-tensor), packed fp32 weight
 // gradients -> torch layout, NCDHW <-> channels-last import / export, copy with the pending affine (concat, materialise),
 // the skinny (<= 8 output channels) pointwise weight gradient, SoundNet's 1-D unfold, fp32 fill.
+#include "conv_host.h"
 #include "elementwise.h"
 
 // ============================================================================
@@ -109,7 +110,6 @@ __global__ __launch_bounds__(256) void pack_weights_multi_kernel(const long* __r
     pack_store<DT>(out, e, v);
   }
 }
-
 
 // ---- LDS-tiled forms of the two multi-tensor kernels (round 4) -----------------------------------------------------------
 // The element-wise kernels above walk the PACKED order: the torch side ([n][c][tap], taps fastest) is then touched with a
@@ -329,7 +329,6 @@ __global__ __launch_bounds__(256) void unpack_wgrad_tiled_kernel(const long* __r
     }
   }
 }
-int g_vinet_opt_pack_tiled = 1;     // LDS-tiled multi-tensor pack / unpack (0 = the element-wise kernels)
 
 extern "C" int vinet_pack_weights_multi(const int64_t* table, int32_t njobs, int64_t total, int32_t dtype, void* stream) {
   VN_CHECK_ARG(table && njobs > 0 && total > 0, "pack_weights_multi: bad arguments");
@@ -597,7 +596,6 @@ extern "C" int vinet_copy_affine(const VinetTensor* src, int32_t src_dtype, Vine
   return vn_launch_status("copy_affine");
 }
 
-
 // fp32 view (+ pending affine) -> hi and lo bf16 planes, hi = bf16(v), lo = bf16(v - hi): the operands of the bf16 kernels when
 // they serve the split-bf16 form (the weight gradient of VINET_F32S runs as three bf16 launches hi*hi + lo*hi + hi*lo that
 // accumulate into one fp32 workspace: engine.py)
@@ -670,8 +668,6 @@ __global__ __launch_bounds__(256) void wgrad_skinny_kernel(TView x, TView dy, lo
     atomicAdd(dw + (long)n * Kp + gg * 8 + e, a);
   }
 }
-
-int g_vinet_opt_wgrad_skinny = 1;   // 0 = off, 2 = every eligible shape (tests)
 
 bool vinet_wgrad_use_skinny(const VinetWgradDesc* d) {
   if (!g_vinet_opt_wgrad_skinny || d->dtype != VINET_BF16 || d->mode != VINET_CONV_GENERIC || d->ntaps != 1 || d->pre.scale || d->pre.relu ||

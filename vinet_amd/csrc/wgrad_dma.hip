@@ -20,10 +20,7 @@
 //   * voxel index -> (b,t,h,w) uses multiply-high fast division.
 #include <type_traits>
 
-#include "common.h"
-
-extern int g_vinet_opt_wgrad_tg;
-extern int g_vinet_opt_tperm;
+#include "conv_host.h"
 
 // (device globals are per translation unit without -fgpu-rdc: own copies of the pad pages)
 __device__ __attribute__((aligned(64))) uint4 g_wg_zero_page[4];
@@ -338,7 +335,6 @@ static int launch_wg(WgradDmaArgs& a, hipStream_t s) {
 }
 
 // pick (tile, taps per group) from the conv geometry
-extern int g_vinet_opt_wgrad_tg;
 // Taps per group, from in-process A/B on ViNet layer shapes (tools/conv_ab.py --wgrad):
 // occupancy beats dY reuse -- 3 taps per group (3 workgroups/CU) is as fast or faster than 9
 // (1 workgroup/CU, LDS-limited) except on the very large-M 3x3 layers, and small-M layers

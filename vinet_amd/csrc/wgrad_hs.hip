@@ -17,7 +17,7 @@
 //   * loads of step ho+1 are issued before the MFMAs of step ho (named registers, unconditional: see wgrad_ts.hip);
 //   * one fp32-atomic flush per workgroup (dw is zero on entry).
 // The padded image makes every access in range: no bounds checks at all.
-#include "common.h"
+#include "conv_host.h"
 
 struct WgradHsArgs {
   const char* x;
@@ -191,8 +191,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_hs_kernel(const WgradHsArgs
         atomicAdd(a.dw + ((long)g * 64 + n) * 32 + col, acc[g][j][r]);
       }
 }
-
-int g_vinet_opt_wgrad_hs = 1;   // 0 = off, 2 = force on every eligible shape (tests)
 
 // VinetWgradDesc::tline == 2: the caller promises taps (0, kh, 0, slice kh), kh = 0..6 (the folded stem)
 bool vinet_wgrad_use_hs(const VinetWgradDesc* d) {

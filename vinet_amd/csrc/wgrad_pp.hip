@@ -21,7 +21,7 @@
 // A pending BN+ReLU on x is applied at fragment time (8 voxels of ONE channel per lane: two
 // scalars), with the NaN-page padding trick of conv_dma.h.  Split-K over voxel ranges with fp32
 // atomics, as in wgrad_dma.hip.
-#include "common.h"
+#include "conv_host.h"
 
 __device__ __attribute__((aligned(64))) uint4 g_wpp_zero_page[4];
 __device__ __attribute__((aligned(64))) uint4 g_wpp_nan_page[4] = {
@@ -382,9 +382,6 @@ static int launch_wpp(const WgradPPArgs& a, hipStream_t s) {
   return vn_launch_status("conv_wgrad_pp");
 }
 
-extern int g_vinet_opt_wgrad_pp;
-extern int g_vinet_opt_tperm;
-int g_vinet_opt_wgrad_pp_cap = 1;   // the 256 x 256 ping-pong weight gradient honours VinetWgradDesc::max_cus (one round of workgroups under a cap)
 #ifdef VINET_CONV_TIMING
 static float* g_wpp_dbg = nullptr;
 extern "C" void vinet_debug_wgrad_ptr(float* p) { g_wpp_dbg = p; }

@@ -19,7 +19,7 @@
 //   * loads of the next row are issued before the MFMAs of the current one (named registers: see wgrad_ts.hip);
 //   * the grid is (kT x Cin/64) groups x workers; a worker keeps its accumulators over all its items and flushes
 //     once with fp32 atomics (dw is zero on entry).
-#include "common.h"
+#include "conv_host.h"
 
 // (16 zero bytes every lane of a DMA can point at: rows past the image)
 __device__ __attribute__((aligned(64))) uint4 g_vinet_zero_page_rs[4];
@@ -456,7 +456,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_rsm_kernel(const WgradRsArg
       }
 }
 
-
 // ---- round 4: the same row-streaming weight gradient with FOUR waves per workgroup -------------------------------------------
 // tools/wrs_phases.py (s_memtime stamps, ablation builds) on the 8-wave kernels above: a step's 54 MFMAs per wave (864 cycles of
 // matrix pipe, 1728 per SIMD with its two waves) take 3600 cycles; without the MFMAs 2400, without the fragment reads 1900 --
@@ -733,9 +732,6 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_rs4_kernel(const WgradRsArg
         if (n0 + n < a.N && c < a.Cin) atomicAdd(a.dw + ((long)(kt * 9 + t) * a.N + n0 + n) * (long)a.Kp + c, acc[t][i][r]);
       }
 }
-
-int g_vinet_opt_wgrad_rs4 = 1;  // the four-wave form for W = 24, 48, 32, 64, 96 (0 = the eight-wave kernels above)
-int g_vinet_opt_wgrad_rs = 1;   // 0 = off, 2 = force on every eligible shape (tests)
 
 // VinetWgradDesc::tline == 4: the caller promises taps (kt, kh-1, kw-1, slice (kt*3 + kh)*3 + kw), kt < ntaps / 9
 bool vinet_wgrad_use_rs(const VinetWgradDesc* d) {

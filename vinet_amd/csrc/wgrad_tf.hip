@@ -15,7 +15,7 @@
 //     9*NTW MFMAs per wave;
 //   * loads of frame t+1 are issued before the MFMAs of frame t (named registers, masked selects: wgrad_rs.hip);
 //   * grid = (channel chunks x output chunks) x workers, never more than one workgroup per CU; one atomic flush.
-#include "common.h"
+#include "conv_host.h"
 
 struct WgradTfArgs {
   const char* x;
@@ -198,8 +198,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_tf_kernel(const WgradTfArgs
         if (n < a.N && c < a.Cin) atomicAdd(a.dw + ((long)g * a.N + n) * (long)a.Kp + c, acc[g][i][r]);
       }
 }
-
-int g_vinet_opt_wgrad_tf = 1;   // 0 = off, 2 = force on every eligible shape (tests)
 
 static int wtf_ntw(int N) { return N > 128 ? 6 : N > 64 ? 4 : 2; }
 

@@ -18,7 +18,7 @@
 //     are position-major, K-major fragments come from ds_read_b64_tr_b16;
 //   * persistent grid: each workgroup loops over (clip, patch) items and flushes its accumulators once, with
 //     fp32 atomics (dw is zero on entry, as for the split-K kernels).
-#include "common.h"
+#include "conv_host.h"
 
 struct WgradTsArgs {
   const char* x;
@@ -182,8 +182,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_ts_kernel(const WgradTsArgs
   }
 }
 
-extern int g_vinet_opt_wgrad_ts;
-
 // the caller promises temporal taps (VinetWgradDesc::tline); everything else is checked here
 bool vinet_wgrad_use_ts(const VinetWgradDesc* d) {
   if (!g_vinet_opt_wgrad_ts || !d->tline || d->dtype != VINET_BF16 || d->mode != VINET_CONV_GENERIC) return false;
@@ -199,7 +197,6 @@ bool vinet_wgrad_use_ts(const VinetWgradDesc* d) {
   return (long)d->dy.B * (HW / 64) >= 2048 && d->dy.T >= 4;      // enough items for a persistent grid, a walk worth its prologue
 }
 
-int g_vinet_opt_wgrad_ts_cap = 0;   // 1 = the persistent grid honours VinetWgradDesc::max_cus (measured: 677.5 -> 675.6 clips/s -- this launch is on the tail of the step, where the weight-gradient stream is the longer one)
 int vinet_launch_wgrad_ts(const VinetWgradDesc* d, hipStream_t s) {
   WgradTsArgs a;
   a.x = (const char*)d->x.ptr; a.dy = (const char*)d->dy.ptr; a.dw = d->dw;
@@ -222,6 +219,7 @@ int vinet_launch_wgrad_ts(const VinetWgradDesc* d, hipStream_t s) {
     if (e != hipSuccess) { vinet_set_error("hipFuncSetAttribute(wgrad_ts): %s", hipGetErrorString(e)); return (int)e; }
     attr_done[dev & 63] = true;
   }
+  // wgrad_ts_cap, default off: 1 = the persistent grid honours VinetWgradDesc::max_cus (measured: 677.5 -> 675.6 clips/s -- this launch is on the tail of the step, where the weight-gradient stream is the longer one)
   int grid = g_vinet_opt_wgrad_ts_cap ? 2 * vn_wgrad_cus(d) : 512;      // two workgroups per CU, on no more CUs than the caller's cap
   if (grid > a.items) grid = a.items;
   if (d->pre.scale) hipLaunchKernelGGL(kp, dim3(grid), dim3(256), smem, s, a);
