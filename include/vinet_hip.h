@@ -32,13 +32,14 @@
 #ifndef VINET_HIP_H
 #define VINET_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define VINET_ABI_VERSION 13   /* 13 (round 6): tline 5 / 1 also promise weight slices < 64; entry points unchanged */
+#define VINET_ABI_VERSION 14   /* 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
 
 enum { VINET_F32 = 0, VINET_BF16 = 1,
        /* conv / weight-gradient descriptors only: fp32 tensors (as VINET_F32), bf16 matrix arithmetic on a two-term split of both
@@ -387,6 +388,27 @@ int vinet_loss_fwd(int32_t which, const float* s, const void* gt, int32_t gt_is_
 int vinet_loss_bwd(int32_t which, const float* s, const void* gt, int32_t gt_is_f64, int32_t B, int32_t n,
                    const double* saved, const float* gscale, float coeff, int32_t accumulate, float* ds, void* stream);
 
+/* ------------------------------------------------------------------------
+ * AUC-Judd (loss.py:122-213), the fifth validation metric; forward only.  One workgroup per map: `s` [B][n] fp32 or
+ * fp64 saliency maps (fp64 is what a map is once jitter noise was added, loss.py:158-160), `fix` [B][n] fp32 or fp64
+ * fixation maps (a fixation is `fix > 0`).  Per map: S <- (S - min) / (max - min) in the dtype of `s`; thresholds
+ * t_0 >= ... >= t_{N-1} = the normalised values at the N fixations; above_i = #{ p : S_p >= t_i };
+ * score = trapz(tp, x = fp), tp = [0, 1/N, ..., 1, 1], fp = [0, ..., (above_i - i - fp_offset) / (n - N), ..., 1], fp64.
+ * `fp_offset` 0 reproduces loss.py:189 (0-based i), 1 the MATLAB original it was ported from (AUC_Judd.m:72 subtracts
+ * the 1-based index).  score[b] is NaN when map b has no fixation, is constant or holds a NaN (loss.py:143-146,
+ * 166-169); n == N divides by zero as numpy does.  nfix[b] = N.  `above` (optional, [B][n] int32) receives the N
+ * counts of each map.  Counts are exact integers and the sum has a fixed order: results are bit-reproducible and a
+ * map's score does not depend on its neighbours in the batch.
+ * Up to 4096 fixations a map is sorted and counted in LDS, beyond that (or with option "auc_ws") in `workspace`, which
+ * must hold vinet_auc_judd_workspace(B, n) bytes (8-byte aligned) in either case.  jitter=True is the caller adding
+ * noise to `s`; normalize=True and toPlot=True have no counterpart (the first raises TypeError in the reference).
+ * auc_shuff (loss.py:215-284) raises TypeError on every input and has no counterpart either.
+ * ---------------------------------------------------------------------- */
+size_t vinet_auc_judd_workspace(int32_t B, int32_t n);
+int vinet_auc_judd(const void* s, int32_t s_is_f64, const void* fix, int32_t fix_is_f64, int32_t B, int32_t n,
+                   int32_t fp_offset, void* workspace, size_t workspace_bytes, double* score, int32_t* nfix,
+                   int32_t* above, void* stream);
+
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) over one flat fp32 buffer
  * (train.py:188,217). bias corrections are passed by the host. */
 int vinet_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
@@ -505,7 +527,8 @@ int vinet_gt_preprocess(const uint8_t* src, int32_t N, int32_t H, int32_t W, flo
  *   "pool_twalk" (1): T-walking 3x3x3/s1 max-pool backward: 0 off, 1 large tensors, 2 always, 3 conditional-load form, 4
  *       bf16 without the EXEC-mask routing
  *   "pool_blk" (1): strided max-pool backward per 2x2 input block; 0 off
- *   "up_blk" (1): 8-channel upsample kernels (forward per 2x2 output block); 0 off */
+ *   "up_blk" (1): 8-channel upsample kernels (forward per 2x2 output block); 0 off
+ *   "auc_ws" (0): AUC-Judd sorts and counts in the caller's workspace whatever the number of fixations: 1 on (tests) */
 int vinet_set_option(const char* name, int32_t value);
 /* fp32 view (with its pending affine applied) -> hi = bf16(v) and lo = bf16(v - hi) planes of the same dims: the operands of
  * the bf16 kernels when they serve the VINET_F32S arithmetic as three accumulating launches (hi*hi + lo*hi + hi*lo; the weight

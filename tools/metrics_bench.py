@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""maps/s of vinet_amd.loss.auc_judd_batch on the device, beside the numpy rank model (tests/auc_model.py) on the host.
+
+    python tools/metrics_bench.py [--reps 20] [--json out.json] [--forward 1]
+
+Shapes: 224x384 / 60 fixations, 360x640 / 900, 1080x1920 / 20 000 (above the kernel's LDS switch point: workspace route),
+each at B = 1 and 64.  Every shape is warmed up; a timing is a host clock around `reps` calls that end in a device
+synchronise.  `--forward 1` also times the ViNet-32 forward (bf16, 224x384) that produces 64 maps, the yardstick the metric
+should stay below.  No GPU: the device columns fail, nothing falls back.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np
+import torch
+
+from tests import auc_model as M
+from vinet_amd import loss, synth
+
+SHAPES = ((224, 384, 60), (360, 640, 900), (1080, 1920, 20000))
+
+
+def _inputs(H, W, nfix, B):
+    s1 = synth.saliency_maps("mb", 1, H, W, 1)
+    f1 = synth.fixation_maps(synth.fixations("mbf", s1, nfix, 1), H, W)
+    return np.repeat(s1, B, 0), np.repeat(f1, B, 0)
+
+
+def _time(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--reps", default=20, type=int)
+    p.add_argument("--json", default=None)
+    p.add_argument("--forward", default=0, type=int)
+    args = p.parse_args()
+    assert torch.cuda.is_available(), "metrics_bench needs the GPU"
+    dev = torch.device("cuda:0")
+    rows = []
+    for H, W, nfix in SHAPES:
+        s1, f1 = _inputs(H, W, nfix, 1)
+        t0 = time.perf_counter()
+        M.auc_judd_rank(s1[0], f1[0])
+        host = time.perf_counter() - t0
+        for B in (1, 64):
+            s, f = (torch.from_numpy(np.repeat(a, B, 0)).to(dev) for a in (s1, f1))
+            noise = torch.rand(s.shape, dtype=torch.float64, device=dev) / 1e7
+            reps = max(3, args.reps // (4 if H >= 1080 else 1))
+            t32 = _time(lambda: loss.auc_judd_batch(s, f), reps)
+            t64 = _time(lambda: loss.auc_judd_batch(s, f, noise=noise), reps)
+            rows.append(dict(H=H, W=W, nfix=nfix, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32, ms_jitter_fp64=t64 * 1e3,
+                             maps_per_s_jitter_fp64=B / t64, numpy_model_ms_per_map_one_core=host * 1e3))
+            print(json.dumps(rows[-1]), flush=True)
+    if args.forward:
+        from vinet_amd import engine, model
+        engine.set_default_dtype("bf16")
+        m = model.VideoSaliencyModel(num_clips=32)
+        m.load_state_dict(synth.synth_state_dict(m.state_dict(), 7))
+        m = m.to(dev).eval()
+        x = synth.clip(1, 32, 224, 384, 0).permute(0, 2, 1, 3, 4).expand(64, -1, -1, -1, -1).contiguous().to(dev)
+        with torch.no_grad():
+            t = _time(lambda: m(x), 3)
+        rows.append(dict(forward_vinet32_bf16_B64_ms=t * 1e3))
+        print(json.dumps(rows[-1]), flush=True)
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(rows, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()

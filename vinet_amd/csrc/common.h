@@ -246,6 +246,60 @@ VN_DEV double wave_sum_d(double v) {
   return v;
 }
 
+// ---- one-workgroup-per-map reductions (loss_adam.hip, metrics.hip): wave shuffles, then a serial pass over the
+// per-wave values in LDS (`sh` / `shi`: one slot per wave, 16 for 1024 lanes).  Fixed order: a result depends on the
+// data alone.  Every lane of the group must call them; the leading barrier lets `sh` be reused back to back.
+VN_DEV int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// ground truth / fixation maps are fp32 or fp64
+template <bool G64> VN_DEV double ldg(const void* gt, long i) {
+  if (G64) return ((const double*)gt)[i];
+  return (double)((const float*)gt)[i];
+}
+
+struct MinIdx { double v; int i; };
+
+VN_DEV double block_sum_d(double v, double* sh) {
+  v = wave_sum_d(v);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  __syncthreads();
+  if (lane == 0) sh[wv] = v;
+  __syncthreads();
+  double r = 0.0;
+  for (int k = 0; k < nw; ++k) r += sh[k];
+  return r;
+}
+VN_DEV MinIdx block_min_d(double v, int idx, double* sh, int* shi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(idx, o, 64);
+    if (ov < v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  __syncthreads();
+  if (lane == 0) { sh[wv] = v; shi[wv] = idx; }
+  __syncthreads();
+  MinIdx r = {sh[0], shi[0]};
+  for (int k = 1; k < nw; ++k)
+    if (sh[k] < r.v || (sh[k] == r.v && shi[k] < r.i)) { r.v = sh[k]; r.i = shi[k]; }
+  return r;
+}
+VN_DEV double block_max_d(double v, double* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  __syncthreads();
+  if (lane == 0) sh[wv] = v;
+  __syncthreads();
+  double r = sh[0];
+  for (int k = 1; k < nw; ++k) r = fmax(r, sh[k]);
+  return r;
+}
+
 // ---- host side -----------------------------------------------------------
 void vinet_set_error(const char* fmt, ...);
 #define VN_CHECK_ARG(cond, ...)            \

@@ -6,6 +6,11 @@ signatures ([B,H,W] maps -> scalar, batch mean) and are differentiable w.r.t.
 with fp64 accumulators (libvinet_hip.so: vinet_loss_fwd / vinet_loss_bwd).
 Ground truth may be float32 or float64 (the DIEM loader hands over float64,
 SURVEY.md F11); like the reference the result is then float64.
+
+The validation metrics `nss` (loss.py:101-120) and `auc_judd` (loss.py:122-213) run on the device too, forward only;
+`auc_judd_batch` scores a whole batch in one launch (libvinet_hip.so: vinet_auc_judd, one workgroup per map, exact
+integer counts).  `auc_shuff` (loss.py:215-284) is left out on purpose: the reference raises TypeError on every input
+(it calls the torch `normalize_map` on a numpy array), so there is nothing to reproduce.
 """
 import torch
 
@@ -85,3 +90,75 @@ def nss(s_map, gt):
     L.check(lib.vinet_loss_fwd(3, s.data_ptr(), g.data_ptr(), 1 if g.dtype == torch.float64 else 0, B, n,
                                saved.data_ptr(), out.data_ptr(), E._stream_for(s.device)), "vinet_loss_fwd")
     return out.double() if g.dtype == torch.float64 else out
+
+
+def _fix_maps(fix):
+    g = fix.detach()
+    if g.dtype not in (torch.float32, torch.float64):
+        g = g.float()
+    return g.contiguous()
+
+
+@torch.no_grad()
+def auc_judd_batch(s_maps, fix_maps, *, noise=None, mit=False, return_counts=False):
+    """AUC-Judd of every map of a batch: `[B,H,W]` float32 or float64 saliency maps, fixation maps of the same size (a
+    fixation is `> 0`) -> float64 `[B]` on the device, NaN where a map has no fixation or is constant.  `noise`: an optional
+    float64 `[B,H,W]` tensor added as `s.double() + noise` first (that is what the reference's jitter is, loss.py:158-160).
+    `mit=True` subtracts the 1-based threshold index as AUC_Judd.m:72 does; the default reproduces loss.py:189.
+    `return_counts`: also the number of fixations `[B]` and the `above` counts `[B, H*W]` (int32, first N valid)."""
+    assert s_maps.size() == fix_maps.size(), "auc_judd: resize the saliency map to the fixation map first"
+    assert s_maps.dim() == 3, "expected [B,H,W] maps"
+    s = s_maps.detach()
+    if noise is not None:
+        assert noise.size() == s.size() and noise.dtype == torch.float64, "noise: a float64 tensor of the maps' size"
+        s = s.double() + noise
+    elif s.dtype not in (torch.float32, torch.float64):
+        s = s.float()
+    s = s.contiguous()
+    g = _fix_maps(fix_maps)
+    B, n = s.shape[0], s.shape[1] * s.shape[2]
+    lib = L.get()
+    ws = torch.empty(max(int(lib.vinet_auc_judd_workspace(B, n)), 8), dtype=torch.uint8, device=s.device)
+    score = torch.empty(B, dtype=torch.float64, device=s.device)
+    nfix = torch.empty(B, dtype=torch.int32, device=s.device)
+    above = torch.empty((B, n), dtype=torch.int32, device=s.device) if return_counts else None
+    L.check(lib.vinet_auc_judd(s.data_ptr(), 1 if s.dtype == torch.float64 else 0, g.data_ptr(), 1 if g.dtype == torch.float64 else 0,
+                               B, n, 1 if mit else 0, ws.data_ptr(), ws.numel(), score.data_ptr(), nfix.data_ptr(),
+                               above.data_ptr() if above is not None else None, E._stream_for(s.device)), "vinet_auc_judd")
+    return (score, nfix, above) if return_counts else score
+
+
+def auc_judd(saliencyMap, fixationMap, jitter=True, toPlot=False, normalize=False):
+    """loss.py:122-213 for maps of equal size: a 2-D map or, of a 3-D batch, item 0 (loss.py:135-137) -> Python float.
+    `jitter=True` adds `torch.rand(float64) / 1e7`, drawn on the maps' device.  Prints the reference's message and returns NaN
+    when there is no fixation or the map is constant."""
+    if toPlot:
+        raise NotImplementedError("auc_judd(toPlot=True) draws with matplotlib on the host; plot the returned score's inputs yourself")
+    if normalize:
+        raise NotImplementedError("auc_judd(normalize=True) raises TypeError in the reference (torch normalize_map on a numpy array)")
+    assert saliencyMap.size() == fixationMap.size(), "auc_judd: resize the saliency map to the fixation map first"
+    assert saliencyMap.dim() in (2, 3), "expected a [H,W] map or a [B,H,W] batch"
+    s = saliencyMap[:1] if saliencyMap.dim() == 3 else saliencyMap.unsqueeze(0)
+    f = fixationMap[:1] if fixationMap.dim() == 3 else fixationMap.unsqueeze(0)
+    noise = torch.rand(s.shape, dtype=torch.float64, device=s.device) / 1e7 if jitter else None
+    score, nfix, _ = auc_judd_batch(s, f, noise=noise, return_counts=True)
+    score, nfix = float(score[0]), int(nfix[0])
+    if score != score:
+        print('Error: no fixationMap' if nfix == 0 else 'NaN saliencyMap')
+    return score
+
+
+@torch.no_grad()
+def per_sample(name, s_map, gt):
+    """The value of `kldiv` / `cc` / `similarity` / `nss` for every map of the batch on its own: float64 `[B]`, what the batched
+    functions average (the forward kernel writes it per sample).  The evaluator needs it to skip NaN frames (diem_val.py:116-129)."""
+    assert s_map.size() == gt.size() and s_map.dim() == 3, "expected [B,H,W] maps of equal size"
+    which = _WHICH[name]
+    s = s_map.detach().float().contiguous()
+    g = _fix_maps(gt)
+    B, n = s.shape[0], s.shape[1] * s.shape[2]
+    saved = torch.empty(B * 8, dtype=torch.float64, device=s.device)
+    out = torch.empty((), dtype=torch.float32, device=s.device)
+    L.check(L.get().vinet_loss_fwd(which, s.data_ptr(), g.data_ptr(), 1 if g.dtype == torch.float64 else 0, B, n,
+                                   saved.data_ptr(), out.data_ptr(), E._stream_for(s.device)), "vinet_loss_fwd")
+    return saved.view(B, 8)[:, 2 if which == 0 else 5].clone()

@@ -15,6 +15,7 @@ weights and biases are fp32 in torch's own layout (`[N, Cin, kT, kH, kW]`), exac
     torch.ops.vinet.maxpool3d / maxpool3d_bwd                            nn.MaxPool3d          model.py:696-714, model_utils.py:178
     torch.ops.vinet.upsample2x / upsample2x_bwd                          nn.Upsample((1,2,2), trilinear)  model.py:254
     torch.ops.vinet.saliency_loss / saliency_loss_bwd                    kldiv / cc / similarity          loss.py:13-99
+    torch.ops.vinet.auc_judd(s_maps, fix_maps, mit)                      AUC-Judd per map (forward only)  loss.py:122-213
     torch.ops.vinet.adam_step_                                           torch.optim.Adam.step over a flat buffer   train.py:188,217
 
 There is no CPU kernel behind them: on a CPU tensor they raise (vinet_amd._lib), except under the tests' ABI double.
@@ -287,6 +288,19 @@ def _loss_backward(ctx, gl, gsaved):
 
 
 saliency_loss.register_autograd(_loss_backward, setup_context=_loss_setup)
+
+
+# ---- AUC-Judd (validation metric: no autograd) ------------------------------------------------------------------------------------
+@torch.library.custom_op("vinet::auc_judd", mutates_args=())
+def auc_judd(s_maps: Tensor, fix_maps: Tensor, mit: bool) -> Tensor:
+    """[B,H,W] saliency maps (fp32 / fp64; add jitter noise before the call) and fixation maps -> fp64 [B] scores, NaN allowed"""
+    from . import loss as VL
+    return VL.auc_judd_batch(s_maps, fix_maps, mit=mit)
+
+
+@auc_judd.register_fake
+def _(s_maps, fix_maps, mit):
+    return s_maps.new_empty((s_maps.shape[0],), dtype=torch.float64)
 
 
 # ---- fused Adam over a flat buffer ----------------------------------------------------------------------------------------------

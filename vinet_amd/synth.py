@@ -138,3 +138,56 @@ def audio(batch, length=70560, seed=0):
     start = (length - n) // 2
     env[start:start + n] = win
     return (w * env).view(batch, 1, length, 1)
+
+
+def saliency_maps(name, batch, height, width, seed=0, levels=0, noise=0.02):
+    """Predicted-saliency stand-ins ``[B, H, W]`` float32 (numpy) for the validation metrics: three rational blobs
+    ``1 / (1 + d^2 / sigma^2)`` plus ``noise`` x uniform, scaled to [0, 1].  ``levels`` > 0 quantises to that many integer
+    levels 0 .. levels-1 (what a decoded PNG holds: heavy ties).  Only +, * and / in float64, so the bits do not depend
+    on the machine's math library."""
+    u = uniform01(name + "/blobs", batch * 9, seed).reshape(batch, 3, 3)
+    ys = np.arange(height, dtype=np.float64).reshape(height, 1)
+    xs = np.arange(width, dtype=np.float64).reshape(1, width)
+    out = np.empty((batch, height, width), dtype=np.float32)
+    for b in range(batch):
+        m = np.zeros((height, width), dtype=np.float64)
+        for j in range(3):
+            cy, cx, sig = u[b, j, 0] * height, u[b, j, 1] * width, (0.04 + 0.10 * u[b, j, 2]) * width
+            dy, dx = ys - cy, xs - cx
+            m = m + 1.0 / (1.0 + (dy * dy + dx * dx) / (sig * sig))
+        m = m + noise * uniform01("%s/noise%d" % (name, b), height * width, seed).reshape(height, width)
+        m = m / m.max()
+        if levels:
+            m = np.floor(m * (levels - 1) + 0.5)
+        out[b] = m.astype(np.float32)
+    return out
+
+
+def fixations(name, smaps, count, seed=0):
+    """``count`` distinct fixated pixels per map, drawn where the map is high (rejection sampling against the map scaled to
+    [0.05, 1]): a list of sorted int64 index arrays into the flattened maps."""
+    res = []
+    for b, m in enumerate(np.asarray(smaps, dtype=np.float64)):
+        flat = m.reshape(-1)
+        p = 0.05 + 0.95 * (flat - flat.min()) / max(float(flat.max() - flat.min()), 1e-300)
+        cand = 32 * count + 1024
+        idx = np.minimum((uniform01("%s/pos%d" % (name, b), cand, seed) * flat.size).astype(np.int64), flat.size - 1)
+        keep = idx[uniform01("%s/acc%d" % (name, b), cand, seed, 1) < p[idx]]
+        _, first = np.unique(keep, return_index=True)
+        keep = keep[np.sort(first)][:count]
+        assert keep.size == count, "fixations: %d of %d drawn; lower the count" % (keep.size, count)
+        res.append(np.sort(keep))
+    return res
+
+
+def fixation_maps(indices, height, width, dtype=np.float32):
+    """binary ``[B, H, W]`` fixation maps (numpy) from per-map index arrays"""
+    out = np.zeros((len(indices), height * width), dtype=dtype)
+    for b, idx in enumerate(indices):
+        out[b, np.asarray(idx, dtype=np.int64)] = 1
+    return out.reshape(len(indices), height, width)
+
+
+def jitter_noise(name, batch, height, width, seed=0):
+    """the ``np.random.random(shape)`` of loss.py:160 as a recorded stream: float64 ``[B, H, W]`` in [0, 1)"""
+    return np.stack([uniform01("%s/jitter%d" % (name, b), height * width, seed).reshape(height, width) for b in range(batch)])
