@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VINET_ABI_VERSION 14   /* 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
+#define VINET_ABI_VERSION 15   /* 15: vinet_transformer_fwd / _bwd / _workspace; 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
 
 enum { VINET_F32 = 0, VINET_BF16 = 1,
        /* conv / weight-gradient descriptors only: fp32 tensors (as VINET_F32), bf16 matrix arithmetic on a two-term split of both
@@ -422,6 +422,45 @@ int vinet_bilinear_fwd(const void* x1, const void* x2, int32_t dtype, const floa
 int vinet_bilinear_bwd(const void* x1, const void* x2, const void* dout, int32_t dtype, const float* w, int32_t B,
                        int32_t C, int32_t I, int32_t J, int32_t O, void* dx1, void* dx2, float* dw, float* dbias,
                        void* stream);
+
+/* ------------------------------------------------------------------------
+ * Transformer fusion of the audio-visual model (model.py:8-69, 211-221, 239-247): PositionalEncoding + a stack of
+ * nn.TransformerEncoderLayer(E, H, F) -- post-norm, ReLU, LayerNorm eps, dropout p at the attention weights, after the
+ * attention projection, between the two linears and after the second -- over S = 32 tokens (the CHANNELS of the
+ * channels-last activation) of E features (its T*H*W positions):  tokens[b][c][f] = x[b][f][c] + pe[c][f].
+ *
+ * x / y (forward) and dy / dx (backward) are channels-last tensors [B][T][H][W][C = S] with T*H*W = E in `dtype`
+ * (VINET_F32S is taken as VINET_F32); everything in between is fp32: exact fp32 products on the fp32-input MFMA, fp32
+ * accumulation, fp32 softmax rows and LayerNorm statistics.
+ * `params` / `grads`: HOST arrays of L * 12 device pointers, per layer in_proj_weight [3E][E], in_proj_bias,
+ * out_proj.weight [E][E], out_proj.bias, linear1.weight [F][E], linear1.bias, linear2.weight [E][F], linear2.bias,
+ * norm1.weight, norm1.bias, norm2.weight, norm2.bias.  Backward ADDS each parameter's gradient into grads[i] (null: skipped),
+ * summing over clips in a fixed order: two runs agree bit for bit.
+ * `ws`: vinet_transformer_workspace(desc) bytes, 16-byte aligned; with train = 1 forward leaves the layers' saved state
+ * there (inputs of every GEMM, softmax rows, LayerNorm statistics) and backward must get the same buffer and descriptor.
+ * Dropout (p > 0, with or without train = 1; pass p = 0 for eval mode): keep masks are a counter-based hash of (seed, *step, layer, site, element), recomputed by
+ * backward.  Forward reads the device counter `step`, keeps the value it drew in the workspace and increments the counter,
+ * so a captured and replayed step draws new masks.  `masks` (optional, forward): receives the keep masks as bytes, per layer
+ * [B][H][S][S] | [B S][E] | [B S][F] | [B S][E].
+ * Limits: S = 32, E % 16 == 0, E <= 384, F % 16 == 0, E / H <= 96.
+ * ---------------------------------------------------------------------- */
+typedef struct VinetTransformerDesc {
+  int32_t dtype;
+  int32_t B, S, E, H, F, L;
+  int32_t train;
+  float p, eps;
+  uint64_t seed;
+  int64_t* step;
+  const float* pe;               /* [S][E] */
+  const void* const* params;
+  void* const* grads;
+  void* ws;
+  int64_t ws_bytes;
+  uint8_t* masks;
+} VinetTransformerDesc;
+int64_t vinet_transformer_workspace(const VinetTransformerDesc* desc);
+int vinet_transformer_fwd(const VinetTransformerDesc* desc, const VinetTensor* x, const VinetTensor* y, void* stream);
+int vinet_transformer_bwd(const VinetTransformerDesc* desc, const VinetTensor* dy, const VinetTensor* dx, void* stream);
 
 /* ------------------------------------------------------------------------
  * Saliency-map post-processing: the host-side cv2 / torchvision steps of

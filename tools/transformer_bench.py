@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Timing of the transformer fusion (bench.py measures the flagship workload and stays as it is).
+
+  encoder   the fused HIP encoder stack (3 layers, 32 tokens x 336 features) forward and forward + backward at B = 1, 8, 32, 192
+            against torch's own nn.TransformerEncoder in eager mode on the same device, weights and input (dropout 0 on both)
+  step      the AViNet training step (kldiv + fused Adam, --dtype) with and without use_transformer at --step_batches (default 1, 8, 32, 192)
+
+Warm-up, then the median of --repeats timed runs (device events around one call).  One JSON line per measurement on stdout.
+
+    python tools/transformer_bench.py [--what encoder,step] [--repeats 30] [--step_batches 1,8,32,192] [--dtype bf16]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch
+
+from vinet_amd import engine as E
+from vinet_amd import fusion, synth
+
+
+def median_ms(fn, warmup, repeats):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return statistics.median(ts), min(ts)
+
+
+def bench_encoder(args, dev):
+    from vinet_amd import model as VM
+    E.set_default_dtype("fp32")
+    tf = VM._TransformerParams(336, hidden_size=336, nhead=4, num_encoder_layers=3, max_len=32)
+    sd = synth.synth_state_dict(tf.state_dict(), 1)
+    sd["pos_encoder.pe"] = tf.state_dict()["pos_encoder.pe"]
+    tf.load_state_dict(sd)
+    for l in tf.transformer_encoder.layers:
+        l.dropout.p = l.dropout1.p = l.dropout2.p = 0.0
+        l.self_attn.dropout = 0.0
+    tf = tf.to(dev).train()
+    aten = torch.nn.TransformerEncoder(torch.nn.TransformerEncoderLayer(336, 4, 336, dropout=0.0), 3).to(dev).train()
+    aten.load_state_dict({k[len("transformer_encoder."):]: v for k, v in sd.items() if k.startswith("transformer_encoder.")})
+    pe = sd["pos_encoder.pe"].to(dev)
+    for B in (1, 8, 32, 192):
+        x = synth.normal("bench_x", (B, 32, 4, 7, 12), 2).to(dev)
+        g = synth.normal("bench_g", (B, 32, 4, 7, 12), 3).to(dev)
+        xt = x.reshape(B, 32, 336).permute(1, 0, 2).contiguous()
+        gt = g.reshape(B, 32, 336).permute(1, 0, 2).contiguous()
+
+        def hip_fwd():
+            with torch.no_grad():
+                return fusion.transformer_tokens(tf, x)
+
+        def hip_fb():
+            xr = x.detach().requires_grad_(True)
+            (fusion.transformer_tokens(tf, xr) * g).sum().backward()
+
+        def aten_fwd():
+            with torch.no_grad():
+                return aten(xt + pe)
+
+        def aten_fb():
+            xr = xt.detach().requires_grad_(True)
+            (aten(xr + pe) * gt).sum().backward()
+
+        row = dict(bench="encoder", B=B)
+        for name, fn in (("hip_fwd", hip_fwd), ("aten_fwd", aten_fwd), ("hip_fwd_bwd", hip_fb), ("aten_fwd_bwd", aten_fb)):
+            med, lo = median_ms(fn, args.warmup, args.repeats)
+            row[name + "_ms"] = round(med, 4)
+            row[name + "_min_ms"] = round(lo, 4)
+        E.LAUNCH_LOG = []
+        hip_fb()
+        row["engine_calls_fwd_bwd"] = len(E.LAUNCH_LOG)
+        E.LAUNCH_LOG = None
+        print(json.dumps(row), flush=True)
+
+
+def bench_step(args, dev):
+    from vinet_amd import loss as VL
+    from vinet_amd import model as VM
+    from vinet_amd import optim as VO
+    E.set_default_dtype(args.dtype)
+    for B in [int(b) for b in args.step_batches.split(",")]:
+        x = synth.clip(B, 32, 224, 384, 5).permute(0, 2, 1, 3, 4).contiguous().to(dev)
+        a = synth.audio(B, 70560, 5).to(dev)
+        gt = synth.gt_map(B, 224, 384, 5).to(dev)
+        row = dict(bench="avinet_step", B=B, dtype=args.dtype)
+        for flag in (False, True):
+            m = VM.VideoAudioSaliencyModel(use_transformer=flag, num_clips=32)
+            sd = synth.synth_state_dict(m.state_dict(), 3)
+            if flag:
+                sd["transformer.pos_encoder.pe"] = m.state_dict()["transformer.pos_encoder.pe"]
+            m.load_state_dict(sd)
+            m = m.to(dev).train()
+            opt = VO.Adam([p for p in m.parameters() if p.requires_grad], lr=1e-5)
+
+            def step():
+                opt.zero_grad()
+                VL.kldiv(m(x, a), gt).backward()
+                opt.step()
+
+            try:
+                med, lo = median_ms(step, 3, args.step_repeats)
+            except torch.OutOfMemoryError:
+                row["oom_%s" % ("on" if flag else "off")] = True
+                del m, opt
+                torch.cuda.empty_cache()
+                continue
+            E.LAUNCH_LOG = []
+            step()
+            row["launches_%s" % ("on" if flag else "off")] = len(E.LAUNCH_LOG)
+            E.LAUNCH_LOG = None
+            row["step_ms_%s" % ("on" if flag else "off")] = round(med, 3)
+            del m, opt
+            torch.cuda.empty_cache()
+        if "step_ms_on" in row and "step_ms_off" in row:
+            row["overhead_ms"] = round(row["step_ms_on"] - row["step_ms_off"], 3)
+        print(json.dumps(row), flush=True)
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--what", default="encoder,step")
+    p.add_argument("--warmup", default=5, type=int)
+    p.add_argument("--repeats", default=30, type=int)
+    p.add_argument("--step_repeats", default=9, type=int)
+    p.add_argument("--step_batches", default="1,8,32,192")
+    p.add_argument("--dtype", default="bf16")
+    args = p.parse_args()
+    dev = torch.device("cuda:0")
+    if "encoder" in args.what:
+        bench_encoder(args, dev)
+    if "step" in args.what:
+        bench_step(args, dev)
+
+
+if __name__ == "__main__":
+    main()

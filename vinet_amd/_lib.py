@@ -16,7 +16,7 @@ F32, BF16 = 0, 1
 F32S = 2     # conv / weight-gradient descriptors: fp32 tensors, split-bf16 matrix arithmetic (include/vinet_hip.h)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 CONV_GENERIC, CONV_STEM = 0, 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class CTensor(C.Structure):
@@ -56,8 +56,16 @@ class CPoolDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32)] + [(n, C.c_int32) for n in ("kT", "kH", "kW", "sT", "sH", "sW", "pT", "pH", "pW")]
 
 
+class CTransformerDesc(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("B", C.c_int32), ("S", C.c_int32), ("E", C.c_int32), ("H", C.c_int32), ("F", C.c_int32),
+                ("L", C.c_int32), ("train", C.c_int32), ("p", C.c_float), ("eps", C.c_float), ("seed", C.c_uint64),
+                ("step", C.c_void_p), ("pe", C.c_void_p), ("params", C.POINTER(C.c_void_p)), ("grads", C.POINTER(C.c_void_p)),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("masks", C.c_void_p)]
+
+
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _PT, _PC, _PW, _PP = C.POINTER(CTensor), C.POINTER(CConvDesc), C.POINTER(CWgradDesc), C.POINTER(CPoolDesc)
+_PX = C.POINTER(CTransformerDesc)
 
 # name -> argtypes (restype is always int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -102,6 +110,9 @@ SIGNATURES = {
     "vinet_adam_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
     "vinet_bilinear_fwd": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "vinet_bilinear_bwd": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "vinet_transformer_workspace": [_PX],
+    "vinet_transformer_fwd": [_PX, _PT, _PT, _vp],
+    "vinet_transformer_bwd": [_PX, _PT, _PT, _vp],
     "vinet_resize_blur": [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp],
     "vinet_minmax": [_vp, _i32, _i64, _vp, _vp],
     "vinet_normalize_u8": [_vp, _vp, _i32, _i64, _vp, _vp],
@@ -120,7 +131,8 @@ SIGNATURES = {
     "vinet_last_error": [],
 }
 _RESTYPE = {"vinet_last_error": C.c_char_p, "vinet_conv3d_splitk_bytes": C.c_int64, "vinet_frames_preprocess_ws_bytes": C.c_int64,
-            "vinet_gt_preprocess_ws_bytes": C.c_int64, "vinet_auc_judd_workspace": C.c_size_t}
+            "vinet_gt_preprocess_ws_bytes": C.c_int64, "vinet_auc_judd_workspace": C.c_size_t,
+            "vinet_transformer_workspace": C.c_int64}
 
 _LIB = None
 _TEST_DOUBLE = None

@@ -1,6 +1,9 @@
 """AViNet audio-visual fusion: nn.Bilinear(42, 3, 336) over channels
-(model.py:230,235-237) as HIP kernels on channels-last tensors."""
+(model.py:230,235-237) and the transformer encoder behind it (model.py:211-221,
+239-247) as HIP kernels on channels-last tensors."""
 import ctypes as C
+
+import torch
 
 from . import _lib as L
 from . import engine as E
@@ -44,3 +47,70 @@ def bilinear_forward(ctx, bil, y0, audio, out_thw):
 def _dense_plain(a):
     v = a.v
     return a.plain and v.ld == v.C and v.sB == v.T * v.H * v.W * v.C
+
+
+# parameter order of one encoder layer in VinetTransformerDesc::params / ::grads (include/vinet_hip.h)
+def _layer_params(layer):
+    a = layer.self_attn
+    return [a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, layer.linear1.weight, layer.linear1.bias,
+            layer.linear2.weight, layer.linear2.bias, layer.norm1.weight, layer.norm1.bias, layer.norm2.weight, layer.norm2.bias]
+
+
+def transformer_forward(ctx, tf, x, masks=None):
+    """x [B,4,7,12,S=32] as it leaves conv_in_1x1 -> Act of the same shape: PositionalEncoding + the encoder stack of `tf`
+    (model._TransformerParams) with the 32 channels as tokens and the 336 positions as features.  Training mode (with or
+    without gradients, like nn.Dropout) draws dropout masks from (tf.dropout_seed, the device step counter); `masks` (uint8, tf.mask_bytes(B)) receives them."""
+    if not _dense_plain(x):
+        x = E.materialize(ctx, x)
+    E._note_reader(ctx, x)
+    xv = x.v
+    layers = list(tf.transformer_encoder.layers)
+    l0 = layers[0]
+    Etok, S = xv.T * xv.H * xv.W, xv.C
+    pe = tf.pos_encoder.pe
+    assert tuple(pe.shape) == (S, 1, Etok), "positional encoding %s does not fit %d tokens x %d features" % (tuple(pe.shape), S, Etok)
+    p = float(l0.dropout.p) if ctx.training else 0.0
+    for l in layers:
+        assert (l.dropout.p, l.dropout1.p, l.dropout2.p, l.self_attn.dropout) == (l0.dropout.p,) * 4, "one dropout probability per stack"
+    params = [q for l in layers for q in _layer_params(l)]
+    assert all(q.dtype == torch.float32 and q.is_contiguous() for q in params)
+    n = len(params)
+    d = L.CTransformerDesc()
+    d.dtype, d.B, d.S, d.E, d.H, d.F, d.L = ctx.dt, xv.B, S, Etok, l0.self_attn.num_heads, l0.linear1.out_features, len(layers)
+    d.train = 1 if ctx.recording else 0
+    d.p, d.eps, d.seed = p, float(l0.norm1.eps), int(tf.dropout_seed) & (2 ** 64 - 1)
+    step = tf.step_counter(ctx.device) if p > 0 else None
+    d.step, d.pe = E._ptr(step), pe.data_ptr()
+    parr = (C.c_void_p * n)(*[q.data_ptr() for q in params])
+    d.params = parr
+    nbytes = ctx.lib.vinet_transformer_workspace(C.byref(d))
+    if nbytes < 0:
+        L.check(-1, "vinet_transformer_workspace")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=ctx.device)
+    d.ws, d.ws_bytes = ws.data_ptr(), nbytes
+    d.masks = E._ptr(masks)
+    out = E.Act(E.View.alloc(xv.B, xv.T, xv.H, xv.W, S, ctx.dt, ctx.device), needs_grad=True)
+    ctx.call("vinet_transformer_fwd", C.byref(d), C.byref(xv.ct()), C.byref(out.v.ct()), ctx.stream)
+    if ctx.recording:
+        def bwd():
+            dg = out.grad_view()
+            assert not x.is_grad_ready(), "the encoder's input has a single consumer"
+            dx = x.grad_view() if x.needs_grad else None
+            grads = [E._param_grad(q) if q.requires_grad else None for q in params]
+            garr = (C.c_void_p * n)(*[E._ptr(g) for g in grads])
+            d.grads, d.masks = garr, None
+            # (d keeps parr / ws / step alive through the closure: the descriptor is the forward's, workspace included)
+            ctx.call("vinet_transformer_bwd", C.byref(d), C.byref(dg.ct()), C.byref(dx.ct()) if dx else None, ctx.stream)
+            E._note_param_grad(ctx, *params)
+            if dx is not None:
+                x.mark_grad_ready()
+        bwd.keep = (parr, ws, step, pe)
+        ctx.record(bwd)
+    return out
+
+
+def transformer_tokens(tf, x, masks=None):
+    """the encoder of `tf` alone as a root call: x [B, 32, 4, 7, 12] fp32 (channel c = token c, positions = features) -> the same
+    shape; differentiable (input and parameters)"""
+    body = E.BlockBody(tf, lambda ctx, a: transformer_forward(ctx, tf, a, masks))
+    return E.run_root(body, [x], list(tf.parameters()))[0]

@@ -200,6 +200,8 @@ def build_parser():
     p.add_argument('--num_hier', default=3, type=int)
     p.add_argument('--clip_size', default=32, type=int)
     p.add_argument('--use_sound', default=False, type=bool)
+    p.add_argument('--use_transformer', default=False, type=bool,
+                   help="the audio-visual model's transformer fusion (needs --use_sound True and --transformer_in_channel 32)")
     p.add_argument('--compute_dtype', default="fp32s", choices=["bf16", "fp32", "fp32s"],
                    help="arithmetic of the HIP path.  Default fp32s (split-bf16 products, fp32 tensors): INSIDE the reference contract -- maps within "
                         "1e-3 of the PyTorch-CPU path, exact argmax.  bf16 is the throughput mode (2.9x faster; maps within 2.5e-2, gradients of the "
@@ -217,7 +219,10 @@ def main(argv=None):
     engine.set_default_dtype(args.compute_dtype)
     kw = dict(transformer_in_channel=args.transformer_in_channel, nhead=args.nhead, use_upsample=bool(args.decoder_upsample),
               num_hier=args.num_hier, num_clips=args.clip_size)
-    m = model.VideoAudioSaliencyModel(**kw) if args.use_sound else model.VideoSaliencyModel(**kw)
+    if args.use_sound:
+        m = model.VideoAudioSaliencyModel(use_transformer=args.use_transformer, num_encoder_layers=args.num_encoder_layers, **kw)
+    else:
+        m = model.VideoSaliencyModel(**kw)
     if os.path.isfile(args.file_weight):
         m.load_state_dict(torch.load(args.file_weight, map_location="cpu"))
     elif args.allow_synthetic_weights:

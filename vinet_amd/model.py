@@ -306,7 +306,8 @@ class SoundNet(nn.Module):
 
 
 class VideoAudioSaliencyModel(nn.Module):
-    """model.py:191-249, use_transformer=False.  Like the reference the constructor
+    """model.py:191-249, with the bilinear fusion alone or (use_transformer=True) followed by conv_in_1x1 -> transformer
+    encoder over the 32 channels -> conv_out_1x1 (model.py:211-221, 239-247).  Like the reference the constructor
     reads the SoundNet weights from ./soundnet8_final.pth (model.py:224) when that
     file is there; the reference fails without it, here the branch then keeps its
     default init and says so (load a full state_dict or call `load_soundnet(path)`)."""
@@ -316,10 +317,17 @@ class VideoAudioSaliencyModel(nn.Module):
     def __init__(self, use_transformer=False, transformer_in_channel=32, num_encoder_layers=3, nhead=4,
                  use_upsample=True, num_hier=3, num_clips=32):
         super().__init__()
-        if use_transformer:
-            raise NotImplementedError("transformer fusion is out of scope (SURVEY.md section 2)")
-        self.use_transformer = False
+        self.use_transformer = bool(use_transformer)
         self.visual_model = VideoSaliencyModel(transformer_in_channel, nhead, use_upsample, num_hier, num_clips)
+        if self.use_transformer:
+            if transformer_in_channel != 32:
+                # model.py:213 builds conv_out_1x1 with in_channels=32 whatever this argument says: any other value fails in forward
+                raise NotImplementedError("use_transformer=True needs transformer_in_channel=32: the reference's conv_out_1x1 has 32 "
+                                          "input channels (model.py:213), got %d" % transformer_in_channel)
+            self.conv_in_1x1 = ConvParams(1024, transformer_in_channel, kernel_size=1, stride=1, bias=True)
+            self.conv_out_1x1 = ConvParams(32, 1024, kernel_size=1, stride=1, bias=True)
+            self.transformer = _TransformerParams(4 * 7 * 12, hidden_size=4 * 7 * 12, nhead=nhead, num_encoder_layers=num_encoder_layers,
+                                                  max_len=transformer_in_channel)
         self.audionet = SoundNet()
         import os
         if os.path.isfile(self.soundnet_checkpoint):
@@ -340,6 +348,11 @@ class VideoAudioSaliencyModel(nn.Module):
         y0, y1, y2, y3 = self.visual_model.backbone._fwd(ctx, x)
         y0 = E.maxpool_forward(ctx, y0, (4, 1, 1), (2, 1, 2), (0, 0, 0))  # [B, 1, 7, 6, 1024]
         fused = bilinear_forward(ctx, self.bilinear, y0, a, (4, 7, 12))
+        if self.use_transformer:
+            from .fusion import transformer_forward
+            tok = E.conv_forward(ctx, self.conv_in_1x1.plan(), fused)            # [B, 4, 7, 12, 32], bias, no BN, no ReLU
+            tok = transformer_forward(ctx, self.transformer, tok)
+            fused = E.conv_forward(ctx, self.conv_out_1x1.plan(), tok)
         return self.visual_model.decoder._fwd(ctx, fused, y1, y2, y3)
 
     def forward(self, x, audio):
@@ -349,4 +362,90 @@ class VideoAudioSaliencyModel(nn.Module):
 
 class _BilinearParams(nn.Bilinear):
     def forward(self, a, b):  # pragma: no cover
+        raise RuntimeError("parameters only")
+
+
+# --------------------------------------------------------------------------
+# transformer fusion (model.py:8-69): parameter holders with the reference's names
+# --------------------------------------------------------------------------
+
+TRANSFORMER_MAX_HEAD_WIDTH = 96      # the attention kernels' LDS tiles (csrc/transformer.hip)
+
+
+def sinusoid_table(n_tokens, n_features):
+    """[n_tokens, n_features] fp32: feature 2i of token t is sin(t w_i), feature 2i + 1 is cos(t w_i), w_i = 10000^(-2i / n_features)
+    (n_features even).  Built as the outer product token index x frequency, sin and cos interleaved along the feature axis."""
+    assert n_features % 2 == 0
+    import math
+    freq = torch.exp(torch.arange(0, n_features, 2, dtype=torch.float32) * (-math.log(10000.0) / n_features))
+    angle = torch.outer(torch.arange(n_tokens, dtype=torch.float32), freq)               # [tokens, features / 2]
+    return torch.stack((angle.sin(), angle.cos()), dim=2).flatten(1)
+
+
+class _PositionalEncodingParams(nn.Module):
+    """model.py:8-26: the sinusoid table `pe` [max_len, 1, feat_size]; its dropout is never applied (model.py:25)."""
+
+    def __init__(self, feat_size, dropout=0.1, max_len=4):
+        super().__init__()
+        self.dropout = _Marker("dropout", p=dropout)
+        self.register_buffer("pe", sinusoid_table(max_len, feat_size).unsqueeze(1).contiguous())
+
+    def forward(self, x):  # pragma: no cover
+        raise RuntimeError("parameters only")
+
+
+class _EncoderLayerParams(nn.TransformerEncoderLayer):
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError("parameters only")
+
+
+class _EncoderStackParams(nn.Module):
+    """nn.TransformerEncoder's parameter layout (`layers.N.*`, no final norm): N independent copies of one initialised layer"""
+
+    def __init__(self, layer, num_layers):
+        super().__init__()
+        import copy
+        self.layers = nn.ModuleList([copy.deepcopy(layer) for _ in range(num_layers)])
+        self.num_layers = num_layers
+
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError("parameters only")
+
+
+class _TransformerParams(nn.Module):
+    """model.py:28-46 with num_decoder_layers=-1, spatial_dim=-1 (all the audio-visual model builds)."""
+
+    def __init__(self, feat_size, hidden_size=256, nhead=4, num_encoder_layers=3, max_len=4):
+        super().__init__()
+        if num_encoder_layers < 1:
+            raise ValueError("num_encoder_layers must be >= 1, got %d" % num_encoder_layers)
+        if nhead < 1 or feat_size % nhead:
+            raise ValueError("nhead = %d does not divide the %d features" % (nhead, feat_size))
+        if feat_size // nhead > TRANSFORMER_MAX_HEAD_WIDTH:
+            raise NotImplementedError("nhead = %d gives heads of width %d; the attention kernels hold heads up to %d wide "
+                                      "(nhead = 4 -> 84 is what the reference trains)" % (nhead, feat_size // nhead, TRANSFORMER_MAX_HEAD_WIDTH))
+        self.pos_encoder = _PositionalEncodingParams(feat_size, max_len=max_len)
+        self.transformer_encoder = _EncoderStackParams(_EncoderLayerParams(feat_size, nhead, hidden_size), num_encoder_layers)
+        self.spatial_dim, self.use_decoder = -1, False
+        self.dropout_seed = torch.initial_seed()      # keep masks are a function of (this seed, the step counter, layer, site, element)
+
+    def step_counter(self, device):
+        """device-resident count of training-mode forwards with dropout: the kernels read and advance it, so a captured and
+        replayed step draws new masks.  It is NOT part of the state_dict (whose keys are the reference's): a run resumed from
+        a checkpoint counts from 0 again, so give it another `dropout_seed` (or restore `step_counter(dev).fill_(n)`) if
+        the masks of the first run must not repeat."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())       # ("cuda" and "cuda:0" are one device)
+        c = self.__dict__.get("_step_counter")
+        if c is None or c.device != device:
+            c = self.__dict__["_step_counter"] = torch.zeros(1, dtype=torch.int64, device=device)
+        return c
+
+    def mask_bytes(self, batch):
+        l = self.transformer_encoder.layers[0]
+        S, Etok, F, H = self.pos_encoder.pe.shape[0], self.pos_encoder.pe.shape[2], l.linear1.out_features, l.self_attn.num_heads
+        return len(self.transformer_encoder.layers) * (batch * H * S * S + batch * S * (2 * Etok + F))
+
+    def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError("parameters only")
