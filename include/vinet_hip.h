@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VINET_ABI_VERSION 15   /* 15: vinet_transformer_fwd / _bwd / _workspace; 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
+#define VINET_ABI_VERSION 16   /* 16: vinet_auc_shuffled, vinet_auc_shuffled_workspace; 15: vinet_transformer_fwd / _bwd / _workspace; 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
 
 enum { VINET_F32 = 0, VINET_BF16 = 1,
        /* conv / weight-gradient descriptors only: fp32 tensors (as VINET_F32), bf16 matrix arithmetic on a two-term split of both
@@ -409,6 +409,41 @@ int vinet_auc_judd(const void* s, int32_t s_is_f64, const void* fix, int32_t fix
                    int32_t fp_offset, void* workspace, size_t workspace_bytes, double* score, int32_t* nfix,
                    int32_t* above, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Shuffled AUC (s-AUC) as the reference's evaluation defines it: code_for_Metrics/AUC_shuffled.m with the other map of
+ * createShuffmap1.m and the removal of the frame's own fixations of eval_diem.m:65.  Forward only.  (The Python auc_shuff,
+ * loss.py:215-284, raises on every input and stays without a counterpart.)
+ *   `s` [B][n] fp32 or fp64 saliency maps, `fix` [B][n] fp32 or fp64 fixation maps (a fixation is `fix > 0`), `other`:
+ *   other-fixation maps of `other_kind` 0 uint8 / 1 fp32 / 2 fp64, map b at element b * other_stride (0: one map for the
+ *   whole batch, else >= n).
+ * Per map: S <- (S - min) / (max - min) in the dtype of `s`; N = #{fix > 0}; other set = { p : other_p > 0 and not
+ * fix_p > 0 }, M its size, K = min(N, M); thresholds t_k = k * step in fp64 for k = 0, 1, ... while t_k <= 1 (at most 2048
+ * of them: step >= 1/2047).  For each of `nsplits` splits: curfix = S at K distinct locations of the other set,
+ * tp_k = #{S at fixations >= t_k} / N, fp_k = #{curfix >= t_k} / K, the points (0,0), (fp_k, tp_k) by descending k, (1,1)
+ * and their trapezoid area in fp64; score[b] = the mean over the splits.  (AUC_shuffled.m stops the sweep at the largest value
+ * present; the thresholds above it add the point (0,0) again, zero area.)  score[b] is NaN when map b has no fixation, is
+ * constant, holds a NaN or has an empty other set.  nfix[b] = N, nother[b] = M.
+ * Where the K locations come from:
+ *   `samples` != NULL: int32 [B][nsplits][kmax], each row K pixel indices followed by -1; the kernel uses them as they are
+ *     (a row that does not hold exactly K indices in [0, n) gives that map NaN);
+ *   `samples` == NULL: the device draw.  Location p of split j of a map with frame id f has the 32-bit key
+ *     mix32(mix32(p ^ k0) + k1) with (k0, k1) a function of (seed, f, j) alone; the K locations of the other set with the
+ *     smallest keys are taken (a radix select; the key is a bijection of p, so there are no ties).  frame_ids: int64 [B] or
+ *     NULL for 0 .. B-1.  A map's score depends on (its data, seed, its frame id) and not on the batch around it.
+ *   `samples_out` (optional, int32 [B][nsplits][kmax]) receives the locations used, in no particular order, padded with -1;
+ *     at most kmax per row are written.
+ * Counts are exact integers, every fp64 sum has a fixed order: results are bit-reproducible.  `workspace` must hold
+ * vinet_auc_shuffled_workspace(B, n, nsplits, step) bytes, 8-byte aligned (0 = invalid arguments): the per-split areas, each
+ * map's counts and the list of its other set.  A workgroup stages that list in LDS up to 8192 locations and reads it from the
+ * workspace beyond that (or with option "sauc_ws").
+ * ---------------------------------------------------------------------- */
+size_t vinet_auc_shuffled_workspace(int32_t B, int32_t n, int32_t nsplits, double step);
+int vinet_auc_shuffled(const void* s, int32_t s_is_f64, const void* fix, int32_t fix_is_f64, const void* other,
+                       int32_t other_kind, int64_t other_stride, int32_t B, int32_t n, int32_t nsplits, double step,
+                       int64_t seed, const int64_t* frame_ids, const int32_t* samples, int32_t kmax, void* workspace,
+                       size_t workspace_bytes, double* score, int32_t* nfix, int32_t* nother, int32_t* samples_out,
+                       void* stream);
+
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) over one flat fp32 buffer
  * (train.py:188,217). bias corrections are passed by the host. */
 int vinet_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
@@ -567,7 +602,8 @@ int vinet_gt_preprocess(const uint8_t* src, int32_t N, int32_t H, int32_t W, flo
  *       bf16 without the EXEC-mask routing
  *   "pool_blk" (1): strided max-pool backward per 2x2 input block; 0 off
  *   "up_blk" (1): 8-channel upsample kernels (forward per 2x2 output block); 0 off
- *   "auc_ws" (0): AUC-Judd sorts and counts in the caller's workspace whatever the number of fixations: 1 on (tests) */
+ *   "auc_ws" (0): AUC-Judd sorts and counts in the caller's workspace whatever the number of fixations: 1 on (tests)
+ *   "sauc_ws" (0): shuffled AUC reads the other-fixation list from the caller's workspace whatever its length: 1 on (tests) */
 int vinet_set_option(const char* name, int32_t value);
 /* fp32 view (with its pending affine applied) -> hi = bf16(v) and lo = bf16(v - hi) planes of the same dims: the operands of
  * the bf16 kernels when they serve the VINET_F32S arithmetic as three accumulating launches (hi*hi + lo*hi + hi*lo; the weight

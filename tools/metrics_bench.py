@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""maps/s of vinet_amd.loss.auc_judd_batch on the device, beside the numpy rank model (tests/auc_model.py) on the host.
+"""maps/s of vinet_amd.loss.auc_judd_batch and auc_shuffled_batch on the device, beside their numpy models (tests/auc_model.py,
+tests/sauc_model.py) on the host.
 
     python tools/metrics_bench.py [--reps 20] [--json out.json] [--forward 1]
 
 Shapes: 224x384 / 60 fixations, 360x640 / 900, 1080x1920 / 20 000 (above the kernel's LDS switch point: workspace route),
-each at B = 1 and 64.  Every shape is warmed up; a timing is a host clock around `reps` calls that end in a device
+each at B = 1 and 64.  s-AUC rows (`--sauc 0` leaves them out): the same shapes with an other set of 600 / 20 000 / 100 000
+locations (a frame against its video's union map), 100 splits, step 0.1, the device draw; the host column is the model fed the
+model of that draw.  Every shape is warmed up; a timing is a host clock around `reps` calls that end in a device
 synchronise.  `--forward 1` also times the ViNet-32 forward (bf16, 224x384) that produces 64 maps, the yardstick the metric
 should stay below.  No GPU: the device columns fail, nothing falls back.
 """
@@ -21,9 +24,11 @@ import numpy as np
 import torch
 
 from tests import auc_model as M
+from tests import sauc_model as SM
 from vinet_amd import loss, synth
 
 SHAPES = ((224, 384, 60), (360, 640, 900), (1080, 1920, 20000))
+SAUC_OTHERS = (600, 20000, 100000)
 
 
 def _inputs(H, W, nfix, B):
@@ -47,6 +52,7 @@ def main():
     p.add_argument("--reps", default=20, type=int)
     p.add_argument("--json", default=None)
     p.add_argument("--forward", default=0, type=int)
+    p.add_argument("--sauc", default=1, type=int)
     args = p.parse_args()
     assert torch.cuda.is_available(), "metrics_bench needs the GPU"
     dev = torch.device("cuda:0")
@@ -64,6 +70,22 @@ def main():
             t64 = _time(lambda: loss.auc_judd_batch(s, f, noise=noise), reps)
             rows.append(dict(H=H, W=W, nfix=nfix, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32, ms_jitter_fp64=t64 * 1e3,
                              maps_per_s_jitter_fp64=B / t64, numpy_model_ms_per_map_one_core=host * 1e3))
+            print(json.dumps(rows[-1]), flush=True)
+    for (H, W, nfix), nother in zip(SHAPES, SAUC_OTHERS if args.sauc else ()):
+        s1, f1 = _inputs(H, W, nfix, 1)
+        so = synth.saliency_maps("mbo", 1, H, W, 12)
+        o1 = synth.fixation_maps(synth.fixations("mbof", so, nother, 12), H, W, dtype=np.uint8)[0]
+        fm, oth = SM.other_set(f1[0], o1)
+        t0 = time.perf_counter()
+        SM.auc_shuffled(s1[0], f1[0], o1, SM.draw(oth, min(int(fm.sum()), oth.size), 0, 0, 100))
+        host = time.perf_counter() - t0
+        o = torch.from_numpy(o1).to(dev)
+        for B in (1, 64):
+            s, f = (torch.from_numpy(np.repeat(a, B, 0)).to(dev) for a in (s1, f1))
+            reps = max(3, args.reps // (4 if H >= 1080 else 1))
+            t32 = _time(lambda: loss.auc_shuffled_batch(s, f, o), reps)
+            rows.append(dict(metric="sAUC", H=H, W=W, nfix=nfix, nother=int(oth.size), splits=100, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32,
+                             numpy_model_ms_per_map_one_core=host * 1e3))
             print(json.dumps(rows[-1]), flush=True)
     if args.forward:
         from vinet_amd import engine, model

@@ -16,7 +16,7 @@ F32, BF16 = 0, 1
 F32S = 2     # conv / weight-gradient descriptors: fp32 tensors, split-bf16 matrix arithmetic (include/vinet_hip.h)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 CONV_GENERIC, CONV_STEM = 0, 1
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class CTensor(C.Structure):
@@ -107,6 +107,9 @@ SIGNATURES = {
     "vinet_loss_bwd": [_i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _f32, _i32, _vp, _vp],
     "vinet_auc_judd_workspace": [_i32, _i32],
     "vinet_auc_judd": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
+    "vinet_auc_shuffled_workspace": [_i32, _i32, _i32, _f64],
+    "vinet_auc_shuffled": [_vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _f64, _i64, _vp, _vp, _i32, _vp, C.c_size_t,
+                           _vp, _vp, _vp, _vp, _vp],
     "vinet_adam_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
     "vinet_bilinear_fwd": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "vinet_bilinear_bwd": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
@@ -131,7 +134,7 @@ SIGNATURES = {
     "vinet_last_error": [],
 }
 _RESTYPE = {"vinet_last_error": C.c_char_p, "vinet_conv3d_splitk_bytes": C.c_int64, "vinet_frames_preprocess_ws_bytes": C.c_int64,
-            "vinet_gt_preprocess_ws_bytes": C.c_int64, "vinet_auc_judd_workspace": C.c_size_t,
+            "vinet_gt_preprocess_ws_bytes": C.c_int64, "vinet_auc_judd_workspace": C.c_size_t, "vinet_auc_shuffled_workspace": C.c_size_t,
             "vinet_transformer_workspace": C.c_int64}
 
 _LIB = None

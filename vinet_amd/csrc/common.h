@@ -262,6 +262,13 @@ template <bool G64> VN_DEV double ldg(const void* gt, long i) {
 
 struct MinIdx { double v; int i; };
 
+// 32-bit finaliser, a bijection of uint32 (xor-shifts and odd multipliers): the counter-based draws of the dropout masks
+// (transformer.hip) and of the shuffled-AUC samples (metrics.hip) are built on it
+VN_DEV uint32_t mix32(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+  return x;
+}
+
 VN_DEV double block_sum_d(double v, double* sh) {
   v = wave_sum_d(v);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;

@@ -1,3 +1,5 @@
+// The validation metrics that need more than one reduction: AUC-Judd (below) and the shuffled AUC (second half of the file).
+//
 // AUC-Judd (loss.py:122-213), the fifth validation metric, as a rank problem: one workgroup (1024 lanes) per map.
 //
 // The reference sweeps one threshold per fixation over the whole map, O(pixels x fixations).  Here, per map S [n] with
@@ -191,4 +193,335 @@ extern "C" int vinet_auc_judd(const void* s, int32_t s_is_f64, const void* fix, 
   else { if (fix_is_f64) AUC_LAUNCH(float, true); else AUC_LAUNCH(float, false); }
 #undef AUC_LAUNCH
   return vn_launch_status("auc_judd");
+}
+
+// ---- shuffled AUC (code_for_Metrics/AUC_shuffled.m, createShuffmap1.m, eval_diem.m:65) ---------------------------------------------
+//
+// Per map: N fixations, the other set { p : O_p > 0 and not F_p > 0 } of size M, K = min(N, M), thresholds t_k = k * step
+// (fp64, k = 0 .. T-1: every k with t_k <= 1).  A normalised value v falls in bin j(v) = #{ k : t_k <= v } in [1, T], found by
+// binary search with the comparison `k * step <= v` itself (never floor(v / step): the two differ where v sits on a threshold).
+// #{ v >= t_k } = #{ j(v) >= k + 1 } is a suffix sum of the bin counts: integers, exact in any order.  Three launches:
+//   sauc_prep_kernel   one workgroup per map: min / max / N / M, the suffix counts of the fixations (the tp side, the same for
+//                      every split) and the other set as a list of pixel indices in ascending order, into the workspace;
+//   sauc_split_kernel  grid (map, split group): per split the K locations (given, or drawn: below), their bin counts, the
+//                      suffix sum and the trapezoid area through the fixed block tree, into the workspace;
+//   sauc_mean_kernel   one lane per map: the mean of the areas in split order.
+// The (map, split) pairs are independent and every sum has a fixed order, so the number of split groups (chosen from B to fill
+// the chip) changes no bit.
+//
+// The draw.  Location p of split j has the key h = mix32(mix32(p ^ k0) + k1), (k0, k1) from (seed, frame id, j): a bijection of
+// p, so the keys of a map's locations are distinct and "the K smallest keys" is a set of exactly K.  The K-th smallest key is
+// found by a radix select over the list, 11 + 11 + 10 bits with a 2048-bin LDS histogram (three passes that recompute the keys:
+// no key list, no sort), and a fourth pass bins the locations whose key is <= it.  K == M takes the whole list.
+//
+// LDS of the split kernel: the list 8192 x 4 B = 32 KB, two count arrays (SAUC_MAX_T + 1) x 4 B = 8 KB each, the radix
+// histogram 8 KB: 56 KB, under the 64 KB a static allocation may take (two groups would fit a CU; the kernel's 79 VGPRs allow one).  A DIEM
+// video's union map has 10^4 .. 10^5 locations: those lists are read from the workspace (L2-resident, coalesced) by the same code.
+#define SAUC_LDS_CAP 8192
+#define SAUC_MAX_T 2048
+#define SAUC_RADIX 2048
+
+struct SaucHead { double lo, range; int32_t N, M, nan, pad; };
+
+VN_DEV bool sauc_other_on(const void* o, int kind, long i) {
+  if (kind == 0) return ((const uint8_t*)o)[i] > 0;
+  if (kind == 1) return ((const float*)o)[i] > 0.f;
+  return ((const double*)o)[i] > 0.0;
+}
+// #{ k in [0, T) : k * step <= v }
+VN_DEV int sauc_bin(double v, double step, int T) {
+  int a = 0, e = T;
+  while (a < e) {
+    const int mid = (a + e) >> 1;
+    if ((double)mid * step <= v) a = mid + 1; else e = mid;
+  }
+  return a;
+}
+// h[j] += 1 for every active lane; whole waves call it.  With few bins (step 0.1 has 12) most lanes hit the same one: a ballot
+// per bin and one atomic per wave instead of 64 serialised ones.
+VN_DEV void sauc_count(int* h, int j, bool active, int nb) {
+  if (nb <= 16) {
+    for (int q = 0; q < nb; ++q) {
+      const unsigned long long m = __ballot(active && j == q);
+      if ((threadIdx.x & 63) == 0 && m) atomicAdd(h + q, __popcll(m));
+    }
+  } else if (active) {
+    atomicAdd(h + j, 1);
+  }
+}
+// h[j] <- sum_{i >= j} h[i], j in [0, nb), in place: a contiguous chunk per lane from the top, the chunk sums scanned over the group
+VN_DEV void sauc_suffix(int* h, int nb, int* shi) {
+  __syncthreads();
+  const int tid = threadIdx.x, chunk = (nb + AUC_LANES - 1) / AUC_LANES;
+  const int r0 = tid * chunk < nb ? tid * chunk : nb, r1 = r0 + chunk < nb ? r0 + chunk : nb;
+  int mine = 0, total;
+  for (int r = r0; r < r1; ++r) mine += h[nb - 1 - r];
+  int run = block_excl_scan_i(mine, shi, &total);
+  for (int r = r0; r < r1; ++r) { run += h[nb - 1 - r]; h[nb - 1 - r] = run; }
+  __syncthreads();
+}
+VN_DEV void sauc_keys(int64_t seed, int64_t frame, int split, uint32_t* k0, uint32_t* k1) {
+  uint32_t x = mix32((uint32_t)seed ^ 0x9e3779b9u);
+  x = mix32(x + (uint32_t)((uint64_t)seed >> 32));
+  x = mix32(x ^ (uint32_t)frame);
+  x = mix32(x + (uint32_t)((uint64_t)frame >> 32));
+  *k0 = mix32(x ^ ((uint32_t)split * 0x85ebca6bu));
+  *k1 = mix32(*k0 + 0x9e3779b9u) ^ x;
+}
+VN_DEV uint32_t sauc_key(uint32_t p, uint32_t k0, uint32_t k1) { return mix32(mix32(p ^ k0) + k1); }
+
+template <typename TS, bool F64>
+__global__ __launch_bounds__(AUC_LANES) void sauc_prep_kernel(const TS* __restrict__ s, const void* fix, const void* oth, int okind, long ostride,
+                                                              int n, double step, int T, int want_list, char* ws, size_t ws_per_map,
+                                                              size_t ws_list_off) {
+  __shared__ int hst[SAUC_MAX_T + 1];
+  __shared__ double sh[16];
+  __shared__ int shi[16];
+  __shared__ int wcnt[16];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const TS* sp = s + (long)b * n;
+  const long fb = (long)b * n, ob = (long)b * ostride;
+  char* wm = ws + (size_t)b * ws_per_map;
+  SaucHead* head = (SaucHead*)wm;
+  int* tpc = (int*)(wm + sizeof(SaucHead));
+  int* list = (int*)(wm + ws_list_off);
+  // each wave walks one contiguous segment in steps of 64: the list below comes out in pixel order without a sort
+  const int seg = (int)(((long)n + AUC_LANES - 1) / AUC_LANES) * 64;
+  const long i0 = (long)wv * seg, i1 = i0 + seg < n ? i0 + seg : n;
+  double mn = INFINITY, mx = -INFINITY;
+  int cnt = 0, bad = 0, co = 0;
+  for (long i = i0 + lane; i < i1; i += 64) {
+    const double v = (double)sp[i];
+    mn = fmin(mn, v); mx = fmax(mx, v);
+    bad |= v != v;
+    const bool f = ldg<F64>(fix, fb + i) > 0.0;
+    cnt += f;
+    co += !f && sauc_other_on(oth, okind, ob + i);
+  }
+  mx = block_max_d(mx, sh);
+  mn = -block_max_d(-mn, sh);
+  int N, nbad;
+  block_excl_scan_i(cnt, shi, &N);
+  block_excl_scan_i(bad, shi, &nbad);
+  co = wave_sum_i(co);
+  if (lane == 0) wcnt[wv] = co;
+  __syncthreads();
+  int M = 0, base = 0;
+  for (int k = 0; k < AUC_LANES / 64; ++k) {
+    if (k < wv) base += wcnt[k];
+    M += wcnt[k];
+  }
+  const TS lo = (TS)mn, range = (TS)mx - (TS)mn;
+  // AUC_shuffled.m:33-36 (no fixation), :46-49 (constant map / NaN), and 0/0 of an empty other set
+  const int nan = N == 0 || nbad || !(range > (TS)0) || M == 0;
+  if (tid == 0) { head->lo = (double)lo; head->range = (double)range; head->N = N; head->M = M; head->nan = nan; head->pad = 0; }
+  if (nan) return;
+  for (int i = tid; i <= T; i += AUC_LANES) hst[i] = 0;
+  __syncthreads();
+  for (long c = i0; c < i1; c += 64) {
+    const long i = c + lane;
+    const bool f = i < i1 && ldg<F64>(fix, fb + i) > 0.0;
+    const int j = f ? sauc_bin(auc_norm<TS>(sp[i], lo, range), step, T) : 0;
+    sauc_count(hst, j, f, T + 1);
+    if (want_list) {
+      const bool o = i < i1 && !f && sauc_other_on(oth, okind, ob + i);
+      const unsigned long long m = __ballot(o);
+      if (o) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (int)i;
+      base += __popcll(m);
+    }
+  }
+  sauc_suffix(hst, T + 1, shi);
+  for (int i = tid; i <= T; i += AUC_LANES) tpc[i] = hst[i];
+}
+
+// the splits g, g + G, ... of one map on a list that lives in LDS or in the workspace (inlined once per address space)
+template <typename TS>
+VN_DEV void sauc_splits(const TS* __restrict__ sp, int n, const int* lp, int N, int M, TS lo, TS range, int nsplits, double step, int T,
+                        int64_t seed, int64_t frame, const int32_t* samples, int kmax, int32_t* samples_out, const int* tpc, int* cnt,
+                        int* rad, int* sel, int* fill, double* sh, int* shi, double* auc) {
+  const int tid = threadIdx.x, K = N < M ? N : M;
+  const double dN = (double)N, dK = (double)K;
+  for (int sp_i = blockIdx.y; sp_i < nsplits; sp_i += gridDim.y) {
+    for (int i = tid; i <= T; i += AUC_LANES) cnt[i] = 0;
+    if (tid == 0) *fill = 0;
+    int32_t* out = samples_out ? samples_out + (long)sp_i * kmax : nullptr;
+    if (samples) {
+      __syncthreads();
+      const int32_t* row = samples + (long)sp_i * kmax;
+      for (int c = 0; c < kmax; c += AUC_LANES) {
+        const int p = c + tid < kmax ? row[c + tid] : -1;
+        const bool act = p >= 0 && p < n;
+        const int j = act ? sauc_bin(auc_norm<TS>(sp[p], lo, range), step, T) : 0;
+        sauc_count(cnt, j, act, T + 1);
+        const unsigned long long m = __ballot(act);
+        if ((tid & 63) == 0 && m) atomicAdd(fill, __popcll(m));
+      }
+    } else {
+      uint32_t k0, k1, kth = 0xffffffffu;
+      sauc_keys(seed, frame, sp_i, &k0, &k1);
+      if (K < M) {
+        // radix select of the K-th smallest key: digits of 11, 11 and 10 bits
+        uint32_t prefix = 0;
+        int need = K;
+        for (int pass = 0; pass < 3; ++pass) {
+          const int bits = pass == 2 ? 10 : 11, shift = pass == 0 ? 21 : pass == 1 ? 10 : 0, nbin = 1 << bits;
+          for (int i = tid; i < nbin; i += AUC_LANES) rad[i] = 0;
+          __syncthreads();
+          for (int i = tid; i < M; i += AUC_LANES) {
+            const uint32_t h = sauc_key((uint32_t)lp[i], k0, k1);
+            if (pass == 0 || (h >> (shift + bits)) == prefix) atomicAdd(rad + ((h >> shift) & (uint32_t)(nbin - 1)), 1);
+          }
+          __syncthreads();
+          const int c0 = 2 * tid < nbin ? rad[2 * tid] : 0, c1 = 2 * tid < nbin ? rad[2 * tid + 1] : 0;
+          int total;
+          const int ex = block_excl_scan_i(c0 + c1, shi, &total);
+          if (ex < need && need <= ex + c0) { sel[0] = 2 * tid; sel[1] = need - ex; }
+          else if (ex + c0 < need && need <= ex + c0 + c1) { sel[0] = 2 * tid + 1; sel[1] = need - ex - c0; }
+          __syncthreads();
+          prefix = (prefix << bits) | (uint32_t)sel[0];
+          need = sel[1];
+          __syncthreads();
+        }
+        kth = prefix;
+      } else {
+        __syncthreads();
+      }
+      for (int c = 0; c < M; c += AUC_LANES) {
+        const int i = c + tid;
+        const int p = i < M ? lp[i] : 0;
+        const bool act = i < M && sauc_key((uint32_t)p, k0, k1) <= kth;
+        const int j = act ? sauc_bin(auc_norm<TS>(sp[p], lo, range), step, T) : 0;
+        sauc_count(cnt, j, act, T + 1);
+        const unsigned long long m = __ballot(act);
+        int slot = 0;
+        if ((tid & 63) == 0 && m) slot = atomicAdd(fill, __popcll(m));
+        slot = __shfl(slot, 0, 64) + __popcll(m & ((1ull << (tid & 63)) - 1ull));
+        if (out && act && slot < kmax) out[slot] = p;
+      }
+    }
+    sauc_suffix(cnt, T + 1, shi);                 // cnt[j] = #{ curfix in bin >= j }; *fill = the locations counted
+    const int got = *fill;
+    if (out && !samples)
+      for (int i = got + tid; i < kmax; i += AUC_LANES) out[i] = -1;
+    // points P_0 = (0,0), P_i = (fp_k, tp_k) with k = T - i for i = 1 .. T, P_{T+1} = (1,1); trapz over the T + 1 intervals
+    double acc = 0.0;
+    for (int i = tid; i <= T; i += AUC_LANES) {
+      const double x0 = i == 0 ? 0.0 : (double)cnt[T - i + 1] / dK, y0 = i == 0 ? 0.0 : (double)tpc[T - i + 1] / dN;
+      const double x1 = i == T ? 1.0 : (double)cnt[T - i] / dK, y1 = i == T ? 1.0 : (double)tpc[T - i] / dN;
+      acc += (x1 - x0) * (y1 + y0) / 2.0;
+    }
+    acc = block_sum_d(acc, sh);
+    if (tid == 0) auc[sp_i] = got == K ? acc : NAN;
+  }
+}
+
+template <typename TS>
+__global__ __launch_bounds__(AUC_LANES) void sauc_split_kernel(const TS* __restrict__ s, int n, int nsplits, double step, int T, int64_t seed,
+                                                               const int64_t* frame_ids, const int32_t* samples, int kmax, int force_ws,
+                                                               char* ws, size_t ws_map0, size_t ws_per_map, size_t ws_list_off,
+                                                               int32_t* samples_out) {
+  __shared__ int lst[SAUC_LDS_CAP];
+  __shared__ int tpc[SAUC_MAX_T + 1];
+  __shared__ int cnt[SAUC_MAX_T + 1];
+  __shared__ int rad[SAUC_RADIX];
+  __shared__ double sh[16];
+  __shared__ int shi[16];
+  __shared__ int sel[2];
+  __shared__ int fill;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const char* wm = ws + ws_map0 + (size_t)b * ws_per_map;
+  const SaucHead* head = (const SaucHead*)wm;
+  const int* list = (const int*)(wm + ws_list_off);
+  int32_t* out = samples_out ? samples_out + (long)b * nsplits * kmax : nullptr;
+  if (head->nan) {                               // sauc_mean_kernel writes the NaN; the sample rows of such a map are empty
+    if (out)
+      for (int sp_i = blockIdx.y; sp_i < nsplits; sp_i += gridDim.y)
+        for (int i = tid; i < kmax; i += AUC_LANES) out[(long)sp_i * kmax + i] = -1;
+    return;
+  }
+  const int N = head->N, M = head->M;
+  const TS lo = (TS)head->lo, range = (TS)head->range;
+  const int* tp_ws = (const int*)(wm + sizeof(SaucHead));
+  for (int i = tid; i <= T; i += AUC_LANES) tpc[i] = tp_ws[i];
+  const int64_t frame = frame_ids ? frame_ids[b] : (int64_t)b;
+  const int32_t* smp = samples ? samples + (long)b * nsplits * kmax : nullptr;
+  double* auc = (double*)ws + (long)b * nsplits;
+  const TS* sp = s + (long)b * n;
+  if (!samples && !force_ws && M <= SAUC_LDS_CAP) {
+    for (int i = tid; i < M; i += AUC_LANES) lst[i] = list[i];
+    __syncthreads();
+    sauc_splits<TS>(sp, n, lst, N, M, lo, range, nsplits, step, T, seed, frame, smp, kmax, out, tpc, cnt, rad, sel, &fill, sh, shi, auc);
+  } else {
+    __syncthreads();
+    sauc_splits<TS>(sp, n, list, N, M, lo, range, nsplits, step, T, seed, frame, smp, kmax, out, tpc, cnt, rad, sel, &fill, sh, shi, auc);
+  }
+}
+
+__global__ void sauc_mean_kernel(const char* ws, size_t ws_map0, size_t ws_per_map, int B, int nsplits, double* __restrict__ score,
+                                 int* __restrict__ nfix, int* __restrict__ nother) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const SaucHead* head = (const SaucHead*)(ws + ws_map0 + (size_t)b * ws_per_map);
+  nfix[b] = head->N;
+  nother[b] = head->M;
+  if (head->nan) { score[b] = NAN; return; }
+  const double* auc = (const double*)ws + (long)b * nsplits;
+  double acc = 0.0;
+  for (int i = 0; i < nsplits; ++i) acc += auc[i];
+  score[b] = acc / (double)nsplits;
+}
+
+// the number of k = 0, 1, ... with k * step <= 1 (0: more than SAUC_MAX_T, or no valid step)
+static int sauc_thresholds(double step) {
+  if (!(step > 0.0 && step <= 1.0) || 1.0 / step > (double)(SAUC_MAX_T - 1)) return 0;
+  int T = (int)(1.0 / step) + 1;
+  while ((double)T * step <= 1.0) ++T;
+  while (T > 1 && (double)(T - 1) * step > 1.0) --T;
+  return T <= SAUC_MAX_T ? T : 0;
+}
+static size_t sauc_pad8(size_t v) { return (v + 7) / 8 * 8; }
+static size_t sauc_list_off(int T) { return sizeof(SaucHead) + sauc_pad8(((size_t)T + 1) * sizeof(int32_t)); }
+static size_t sauc_ws_per_map(int32_t n, int T) { return sauc_list_off(T) + sauc_pad8((size_t)n * sizeof(int32_t)); }
+
+extern "C" size_t vinet_auc_shuffled_workspace(int32_t B, int32_t n, int32_t nsplits, double step) {
+  const int T = sauc_thresholds(step);
+  if (B <= 0 || n <= 0 || n > (1 << 30) || nsplits <= 0 || T == 0) return 0;
+  return (size_t)B * nsplits * sizeof(double) + (size_t)B * sauc_ws_per_map(n, T);
+}
+
+extern "C" int vinet_auc_shuffled(const void* s, int32_t s_is_f64, const void* fix, int32_t fix_is_f64, const void* other,
+                                  int32_t other_kind, int64_t other_stride, int32_t B, int32_t n, int32_t nsplits, double step,
+                                  int64_t seed, const int64_t* frame_ids, const int32_t* samples, int32_t kmax, void* workspace,
+                                  size_t workspace_bytes, double* score, int32_t* nfix, int32_t* nother, int32_t* samples_out,
+                                  void* stream) {
+  VN_CHECK_ARG(s && fix && other && score && nfix && nother, "auc_shuffled: null map, fixation map, other map, score, nfix or nother");
+  VN_CHECK_ARG(B > 0 && n > 0 && n <= (1 << 30) && nsplits > 0, "auc_shuffled: B, n and nsplits must be positive (n <= 2^30)");
+  VN_CHECK_ARG(step > 0.0 && step <= 1.0, "auc_shuffled: step must lie in (0, 1]");
+  const int T = sauc_thresholds(step);
+  VN_CHECK_ARG(T > 0, "auc_shuffled: step %g gives more than %d thresholds", step, SAUC_MAX_T);
+  VN_CHECK_ARG(other_kind >= 0 && other_kind <= 2, "auc_shuffled: other_kind is 0 (uint8), 1 (fp32) or 2 (fp64)");
+  VN_CHECK_ARG(other_stride == 0 || other_stride >= n, "auc_shuffled: other_stride is 0 (one map for the batch) or >= n");
+  VN_CHECK_ARG((!samples && !samples_out) || kmax > 0, "auc_shuffled: kmax must be positive with samples or samples_out");
+  VN_CHECK_ARG(!(samples && samples_out), "auc_shuffled: samples_out returns the device draw; the given samples are the caller's already");
+  const size_t need = vinet_auc_shuffled_workspace(B, n, nsplits, step);
+  VN_CHECK_ARG(workspace && workspace_bytes >= need && (((uintptr_t)workspace) & 7) == 0,
+               "auc_shuffled: workspace of %zu bytes (8-byte aligned) needed, got %zu", need, workspace ? workspace_bytes : (size_t)0);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t map0 = (size_t)B * nsplits * sizeof(double), per = sauc_ws_per_map(n, T), loff = sauc_list_off(T);
+  char* ws = (char*)workspace;
+  // split groups per map: enough workgroups for the chip's 256 CUs x 2 whatever B is; the result does not depend on it
+  int G = 2048 / B;
+  G = G < 1 ? 1 : (G > 32 ? 32 : G);
+  G = G > nsplits ? nsplits : G;
+  const int want_list = samples ? 0 : 1;
+#define SAUC_PREP(TS, F64) \
+  hipLaunchKernelGGL((sauc_prep_kernel<TS, F64>), dim3(B), dim3(AUC_LANES), 0, st, (const TS*)s, fix, other, other_kind, (long)other_stride, n, step, T, want_list, ws + map0, per, loff)
+#define SAUC_SPLIT(TS) \
+  hipLaunchKernelGGL((sauc_split_kernel<TS>), dim3(B, G), dim3(AUC_LANES), 0, st, (const TS*)s, n, nsplits, step, T, seed, frame_ids, samples, kmax, g_vinet_opt_sauc_ws, ws, map0, per, loff, samples_out)
+  if (s_is_f64) { if (fix_is_f64) SAUC_PREP(double, true); else SAUC_PREP(double, false); SAUC_SPLIT(double); }
+  else { if (fix_is_f64) SAUC_PREP(float, true); else SAUC_PREP(float, false); SAUC_SPLIT(float); }
+#undef SAUC_PREP
+#undef SAUC_SPLIT
+  hipLaunchKernelGGL(sauc_mean_kernel, dim3((B + 63) / 64), dim3(64), 0, st, ws, map0, per, B, nsplits, score, nfix, nother);
+  return vn_launch_status("auc_shuffled");
 }

@@ -52,7 +52,8 @@
   VN_OPT(pool_twalk,   1, "T-walking 3x3x3/s1 max-pool backward: 0 off, 1 large tensors, 2 always, 3 conditional-load form, 4 bf16 without the EXEC-mask routing") \
   VN_OPT(pool_blk,     1, "strided max-pool backward per 2x2 input block; 0 off") \
   VN_OPT(up_blk,       1, "8-channel upsample kernels (forward per 2x2 output block); 0 off") \
-  VN_OPT(auc_ws,       0, "AUC-Judd sorts and counts in the caller's workspace whatever the number of fixations: 1 on (tests); 0 = in LDS up to 4096 fixations")
+  VN_OPT(auc_ws,       0, "AUC-Judd sorts and counts in the caller's workspace whatever the number of fixations: 1 on (tests); 0 = in LDS up to 4096 fixations") \
+  VN_OPT(sauc_ws,      0, "shuffled AUC reads the other-fixation list from the caller's workspace whatever its length: 1 on (tests); 0 = staged in LDS up to 8192 locations")
 
 #define VN_OPT_DECLARE(name, dflt, text) extern int g_vinet_opt_##name;
 VN_OPTIONS(VN_OPT_DECLARE)

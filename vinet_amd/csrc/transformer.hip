@@ -33,10 +33,6 @@ struct Drop {
   uint32_t seed_lo, seed_hi, thr;
   float scale;             // 1 / (1 - p)
 };
-VN_DEV uint32_t mix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
 struct DropKey { uint32_t k0, k1, thr; float scale; };
 VN_DEV DropKey drop_key(const Drop& d, int stream) {
   DropKey k;

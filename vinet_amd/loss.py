@@ -10,7 +10,9 @@ SURVEY.md F11); like the reference the result is then float64.
 The validation metrics `nss` (loss.py:101-120) and `auc_judd` (loss.py:122-213) run on the device too, forward only;
 `auc_judd_batch` scores a whole batch in one launch (libvinet_hip.so: vinet_auc_judd, one workgroup per map, exact
 integer counts).  `auc_shuff` (loss.py:215-284) is left out on purpose: the reference raises TypeError on every input
-(it calls the torch `normalize_map` on a numpy array), so there is nothing to reproduce.
+(it calls the torch `normalize_map` on a numpy array), so there is nothing to reproduce.  The shuffled AUC that the
+reference's evaluation does compute is the MATLAB one (code_for_Metrics/AUC_shuffled.m, called from eval_diem.m): that is
+`auc_shuffled` / `auc_shuffled_batch` here (libvinet_hip.so: vinet_auc_shuffled), with `shuffle_map` for createShuffmap1.m.
 """
 import torch
 
@@ -145,6 +147,94 @@ def auc_judd(saliencyMap, fixationMap, jitter=True, toPlot=False, normalize=Fals
     score, nfix = float(score[0]), int(nfix[0])
     if score != score:
         print('Error: no fixationMap' if nfix == 0 else 'NaN saliencyMap')
+    return score
+
+
+def shuffle_map(fix_maps):
+    """createShuffmap1.m: the union of a video's fixation maps, `[T,H,W]` (a fixation is `> 0`) -> uint8 `[H,W]`.  The frame's
+    own fixations (eval_diem.m:65) are taken out by the kernel, per map."""
+    assert fix_maps.dim() == 3, "expected [T,H,W] fixation maps"
+    return (fix_maps > 0).any(dim=0).to(torch.uint8)
+
+
+@torch.no_grad()
+def auc_shuffled_batch(s_maps, fix_maps, other_map, *, n_splits=100, step=0.1, seed=0, frame_ids=None, samples=None,
+                       return_samples=False, return_counts=False):
+    """Shuffled AUC (AUC_shuffled.m) of every map of a batch: `[B,H,W]` float32 or float64 saliency maps, fixation maps of the
+    same size, `other_map` `[H,W]` (one for the batch) or `[B,H,W]`, uint8 / bool / float32 / float64 -> float64 `[B]` on the
+    device.  A map's other set is `other > 0 and not fix > 0` (eval_diem.m:65), K = min(fixations, other set); NaN where a map
+    has no fixation, is constant, holds a NaN or has an empty other set.
+    The K locations of each of the `n_splits` splits are drawn on the device as a function of (`seed`, the map's frame id,
+    split, pixel) -- `frame_ids`: int64 `[B]`, default 0 .. B-1; a map's score does not depend on the batch around it -- or
+    taken from `samples`: int32 `[B, n_splits, kmax]`, each row K pixel indices then -1.
+    `return_counts`: also the fixations `[B]` and the other set's size `[B]` (int32); `return_samples`: those and the drawn
+    locations, int32 `[B, n_splits, max K]`, each row ascending and padded with -1."""
+    assert s_maps.size() == fix_maps.size(), "auc_shuffled: resize the saliency map to the fixation map first"
+    assert s_maps.dim() == 3, "expected [B,H,W] maps"
+    assert other_map.dim() in (2, 3) and tuple(other_map.shape[-2:]) == tuple(s_maps.shape[1:]), "other_map: [H,W] or [B,H,W] of the maps' size"
+    assert other_map.dim() == 2 or other_map.shape[0] == s_maps.shape[0], "other_map: one map, or one per saliency map"
+    assert samples is None or not return_samples, "return_samples returns the device draw"
+    s = s_maps.detach()
+    if s.dtype not in (torch.float32, torch.float64):
+        s = s.float()
+    s = s.contiguous()
+    g = _fix_maps(fix_maps)
+    o = other_map.detach()
+    if o.dtype == torch.bool:
+        o = o.to(torch.uint8)
+    elif o.dtype not in (torch.uint8, torch.float32, torch.float64):
+        o = o.float()
+    o = o.contiguous()
+    if o.device != s.device:
+        raise ValueError("auc_shuffled: other_map on %s, the maps on %s" % (o.device, s.device))
+    B, n = s.shape[0], s.shape[1] * s.shape[2]
+    dev = s.device
+    lib = L.get()
+    fid = None
+    if frame_ids is not None:
+        fid = torch.as_tensor(frame_ids, dtype=torch.int64).to(dev).contiguous()
+        assert tuple(fid.shape) == (B,), "frame_ids: one int64 per map"
+    smp = out = None
+    kmax = 0
+    if samples is not None:
+        assert samples.dim() == 3 and tuple(samples.shape[:2]) == (B, n_splits) and samples.shape[2] > 0, "samples: [B, n_splits, kmax]"
+        smp = samples.detach().to(device=dev, dtype=torch.int32).contiguous()
+        kmax = smp.shape[2]
+    elif return_samples:
+        kmax = max(int((g > 0).flatten(1).sum(1).max()), 1)          # K <= N
+        out = torch.empty((B, n_splits, kmax), dtype=torch.int32, device=dev)
+    need = int(lib.vinet_auc_shuffled_workspace(B, n, int(n_splits), float(step)))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    score = torch.empty(B, dtype=torch.float64, device=dev)
+    nfix = torch.empty(B, dtype=torch.int32, device=dev)
+    nother = torch.empty(B, dtype=torch.int32, device=dev)
+    L.check(lib.vinet_auc_shuffled(s.data_ptr(), 1 if s.dtype == torch.float64 else 0, g.data_ptr(), 1 if g.dtype == torch.float64 else 0,
+                                   o.data_ptr(), {torch.uint8: 0, torch.float32: 1, torch.float64: 2}[o.dtype], 0 if o.dim() == 2 else n,
+                                   B, n, int(n_splits), float(step), int(seed), fid.data_ptr() if fid is not None else None,
+                                   smp.data_ptr() if smp is not None else None, kmax, ws.data_ptr(), need, score.data_ptr(),
+                                   nfix.data_ptr(), nother.data_ptr(), out.data_ptr() if out is not None else None,
+                                   E._stream_for(dev)), "vinet_auc_shuffled")
+    if return_samples:
+        # the kernel fills a row in no particular order: ascending, the -1 padding last
+        big = torch.iinfo(torch.int32).max
+        srt = torch.where(out < 0, torch.full_like(out, big), out).sort(dim=2).values
+        return score, nfix, nother, torch.where(srt == big, torch.full_like(srt, -1), srt)
+    return (score, nfix, nother) if return_counts else score
+
+
+def auc_shuffled(saliencyMap, fixationMap, otherMap, Nsplits=100, stepSize=0.1):
+    """AUC_shuffled.m's signature for maps of equal size (2-D, or item 0 of a 3-D batch as `auc_judd` takes it) -> Python float.
+    `otherMap` is used as eval_diem.m:64-71 hands it over: locations that are fixations of this map do not count.  Prints the
+    MATLAB messages and returns NaN when there is no fixation or the map is constant; toPlot has no counterpart."""
+    assert saliencyMap.size() == fixationMap.size(), "auc_shuffled: resize the saliency map to the fixation map first"
+    assert saliencyMap.dim() in (2, 3), "expected a [H,W] map or a [B,H,W] batch"
+    s = saliencyMap[:1] if saliencyMap.dim() == 3 else saliencyMap.unsqueeze(0)
+    f = fixationMap[:1] if fixationMap.dim() == 3 else fixationMap.unsqueeze(0)
+    o = otherMap[0] if otherMap.dim() == 3 else otherMap
+    score, nfix, _ = auc_shuffled_batch(s, f, o, n_splits=Nsplits, step=stepSize, return_counts=True)
+    score, nfix = float(score[0]), int(nfix[0])
+    if score != score:
+        print('no fixationMap' if nfix == 0 else 'NaN saliencyMap')
     return score
 
 

@@ -16,6 +16,7 @@ weights and biases are fp32 in torch's own layout (`[N, Cin, kT, kH, kW]`), exac
     torch.ops.vinet.upsample2x / upsample2x_bwd                          nn.Upsample((1,2,2), trilinear)  model.py:254
     torch.ops.vinet.saliency_loss / saliency_loss_bwd                    kldiv / cc / similarity          loss.py:13-99
     torch.ops.vinet.auc_judd(s_maps, fix_maps, mit)                      AUC-Judd per map (forward only)  loss.py:122-213
+    torch.ops.vinet.auc_shuffled(s_maps, fix_maps, other_map, n_splits, step, seed, frame_ids)   s-AUC per map   AUC_shuffled.m
     torch.ops.vinet.adam_step_                                           torch.optim.Adam.step over a flat buffer   train.py:188,217
 
 There is no CPU kernel behind them: on a CPU tensor they raise (vinet_amd._lib), except under the tests' ABI double.
@@ -300,6 +301,20 @@ def auc_judd(s_maps: Tensor, fix_maps: Tensor, mit: bool) -> Tensor:
 
 @auc_judd.register_fake
 def _(s_maps, fix_maps, mit):
+    return s_maps.new_empty((s_maps.shape[0],), dtype=torch.float64)
+
+
+# ---- shuffled AUC (validation metric: no autograd) ----------------------------------------------------------------------------------
+@torch.library.custom_op("vinet::auc_shuffled", mutates_args=())
+def auc_shuffled(s_maps: Tensor, fix_maps: Tensor, other_map: Tensor, n_splits: int, step: float, seed: int,
+                 frame_ids: Optional[Tensor]) -> Tensor:
+    """[B,H,W] saliency and fixation maps, an other-fixation map [H,W] or [B,H,W] -> fp64 [B] scores of the device draw, NaN allowed"""
+    from . import loss as VL
+    return VL.auc_shuffled_batch(s_maps, fix_maps, other_map, n_splits=n_splits, step=step, seed=seed, frame_ids=frame_ids)
+
+
+@auc_shuffled.register_fake
+def _(s_maps, fix_maps, other_map, n_splits, step, seed, frame_ids):
     return s_maps.new_empty((s_maps.shape[0],), dtype=torch.float64)
 
 
