@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VINET_ABI_VERSION 16   /* 16: vinet_auc_shuffled, vinet_auc_shuffled_workspace; 15: vinet_transformer_fwd / _bwd / _workspace; 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
+#define VINET_ABI_VERSION 16   /* still 16: vinet_auc_borji, vinet_auc_borji_workspace and vinet_info_gain are pure additions (no existing entry point or struct changed); 16: vinet_auc_shuffled, vinet_auc_shuffled_workspace; 15: vinet_transformer_fwd / _bwd / _workspace; 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
 
 enum { VINET_F32 = 0, VINET_BF16 = 1,
        /* conv / weight-gradient descriptors only: fp32 tensors (as VINET_F32), bf16 matrix arithmetic on a two-term split of both
@@ -443,6 +443,40 @@ int vinet_auc_shuffled(const void* s, int32_t s_is_f64, const void* fix, int32_t
                        int64_t seed, const int64_t* frame_ids, const int32_t* samples, int32_t kmax, void* workspace,
                        size_t workspace_bytes, double* score, int32_t* nfix, int32_t* nother, int32_t* samples_out,
                        void* stream);
+
+/* ------------------------------------------------------------------------
+ * AUC-Borji (code_for_Metrics/AUC_Borji.m).  Forward only.  `s`, `fix`, the normalisation, the thresholds t_k = k * step, the
+ * `>=` comparisons and the trapezoid sum are those of vinet_auc_shuffled; what differs is the set of negative locations: for
+ * each of `nsplits` splits N = #{fix > 0} locations drawn from ALL n pixels, uniformly and with replacement (AUC_Borji.m:58,
+ * MATLAB's randi: a fixation pixel may be drawn, a pixel may repeat), and tp and fp are both divided by N.  score[b] = the mean
+ * of the splits' areas in split order; NaN when map b has at most ONE fixation (AUC_Borji.m:31), is constant or holds a NaN.
+ * nfix[b] = N.
+ *   `samples` != NULL: int32 [B][nsplits][kmax], each row N pixel indices followed by -1, used as they are (a row that does
+ *     not hold exactly N indices in [0, n) gives that map NaN);
+ *   `samples` == NULL: the device draw.  Sample j of split q of a map with frame id f is pixel ((uint64)h * n) >> 32 with
+ *     h = mix32(mix32(j ^ k0) + k1); (k0, k1) are the shuffled AUC's function of (seed', f, q) with
+ *     seed' = seed ^ 0x426f726a69415543, so that the two metrics do not share a stream under one seed.  frame_ids: int64 [B]
+ *     or NULL for 0 .. B-1.  A map's score depends on (its data, seed, its frame id) and not on the batch around it.
+ *   `samples_out` (optional, int32 [B][nsplits][kmax]) receives sample j at position j, padded with -1; at most kmax per row.
+ * Counts are exact integers, every fp64 sum has a fixed order: results are bit-reproducible.  `workspace` must hold
+ * vinet_auc_borji_workspace(B, n, nsplits, step) bytes, 8-byte aligned (0 = invalid arguments).
+ * ---------------------------------------------------------------------- */
+size_t vinet_auc_borji_workspace(int32_t B, int32_t n, int32_t nsplits, double step);
+int vinet_auc_borji(const void* s, int32_t s_is_f64, const void* fix, int32_t fix_is_f64, int32_t B, int32_t n, int32_t nsplits,
+                    double step, int64_t seed, const int64_t* frame_ids, const int32_t* samples, int32_t kmax, void* workspace,
+                    size_t workspace_bytes, double* score, int32_t* nfix, int32_t* samples_out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Information gain (code_for_Metrics/InfoGain.m, IG.m).  Forward only.  `s` [B][n] and `fix` [B][n] fp32 or fp64; `baseline`
+ * fp32 or fp64, map b at element b * baseline_stride (0: one map for the whole batch, else >= n), or NULL (IG.m:28-31).
+ * All arithmetic in fp64 on the input values: v = (s - min) / (max - min), p = v / sum(v), the same for the baseline (pb);
+ * score[b] = mean over { fix > 0 } of log2(eps + p) - log2(eps + pb), eps = 2^-52; without a baseline the second term is
+ * absent.  NaN when map b has no fixation, the map or its baseline is constant, or either holds a NaN.  nfix[b] = N.
+ * One workgroup per map, sums in a fixed order: bit-reproducible, independent of the batch.  No workspace.
+ * ---------------------------------------------------------------------- */
+int vinet_info_gain(const void* s, int32_t s_is_f64, const void* fix, int32_t fix_is_f64, const void* baseline,
+                    int32_t baseline_is_f64, int64_t baseline_stride, int32_t B, int32_t n, double* score, int32_t* nfix,
+                    void* stream);
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) over one flat fp32 buffer
  * (train.py:188,217). bias corrections are passed by the host. */

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""maps/s of vinet_amd.loss.auc_judd_batch and auc_shuffled_batch on the device, beside their numpy models (tests/auc_model.py,
-tests/sauc_model.py) on the host.
+"""maps/s of vinet_amd.loss.auc_judd_batch, auc_shuffled_batch, auc_borji_batch and info_gain_batch on the device, beside their
+numpy models (tests/auc_model.py, tests/sauc_model.py, tests/borji_ig_model.py) on the host.
 
     python tools/metrics_bench.py [--reps 20] [--json out.json] [--forward 1]
 
 Shapes: 224x384 / 60 fixations, 360x640 / 900, 1080x1920 / 20 000 (above the kernel's LDS switch point: workspace route),
 each at B = 1 and 64.  s-AUC rows (`--sauc 0` leaves them out): the same shapes with an other set of 600 / 20 000 / 100 000
 locations (a frame against its video's union map), 100 splits, step 0.1, the device draw; the host column is the model fed the
-model of that draw.  Every shape is warmed up; a timing is a host clock around `reps` calls that end in a device
+model of that draw.  AUC-Borji and information-gain rows (`--borji 0` / `--ig 0` leave them out): the same shapes; AUC-Borji with
+100 splits, step 0.1, the device draw; the information gain with one baseline map for the batch.  Every shape is warmed up; a timing is a host clock around `reps` calls that end in a device
 synchronise.  `--forward 1` also times the ViNet-32 forward (bf16, 224x384) that produces 64 maps, the yardstick the metric
 should stay below.  No GPU: the device columns fail, nothing falls back.
 """
@@ -24,6 +25,7 @@ import numpy as np
 import torch
 
 from tests import auc_model as M
+from tests import borji_ig_model as BM
 from tests import sauc_model as SM
 from vinet_amd import loss, synth
 
@@ -53,6 +55,8 @@ def main():
     p.add_argument("--json", default=None)
     p.add_argument("--forward", default=0, type=int)
     p.add_argument("--sauc", default=1, type=int)
+    p.add_argument("--borji", default=1, type=int)
+    p.add_argument("--ig", default=1, type=int)
     args = p.parse_args()
     assert torch.cuda.is_available(), "metrics_bench needs the GPU"
     dev = torch.device("cuda:0")
@@ -85,6 +89,32 @@ def main():
             reps = max(3, args.reps // (4 if H >= 1080 else 1))
             t32 = _time(lambda: loss.auc_shuffled_batch(s, f, o), reps)
             rows.append(dict(metric="sAUC", H=H, W=W, nfix=nfix, nother=int(oth.size), splits=100, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32,
+                             numpy_model_ms_per_map_one_core=host * 1e3))
+            print(json.dumps(rows[-1]), flush=True)
+    for H, W, nfix in (SHAPES if args.borji else ()):
+        s1, f1 = _inputs(H, W, nfix, 1)
+        t0 = time.perf_counter()
+        BM.auc_borji(s1[0], f1[0], BM.draw(H * W, nfix, 0, 0, 100))
+        host = time.perf_counter() - t0
+        for B in (1, 64):
+            s, f = (torch.from_numpy(np.repeat(a, B, 0)).to(dev) for a in (s1, f1))
+            reps = max(3, args.reps // (4 if H >= 1080 else 1))
+            t32 = _time(lambda: loss.auc_borji_batch(s, f), reps)
+            rows.append(dict(metric="AUCB", H=H, W=W, nfix=nfix, splits=100, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32,
+                             numpy_model_ms_per_map_one_core=host * 1e3))
+            print(json.dumps(rows[-1]), flush=True)
+    for H, W, nfix in (SHAPES if args.ig else ()):
+        s1, f1 = _inputs(H, W, nfix, 1)
+        b1 = synth.saliency_maps("mbb", 1, H, W, 9, noise=0.0)[0]
+        t0 = time.perf_counter()
+        BM.info_gain(s1[0], f1[0], b1)
+        host = time.perf_counter() - t0
+        base = torch.from_numpy(b1).to(dev)
+        for B in (1, 64):
+            s, f = (torch.from_numpy(np.repeat(a, B, 0)).to(dev) for a in (s1, f1))
+            reps = max(3, args.reps // (4 if H >= 1080 else 1))
+            t32 = _time(lambda: loss.info_gain_batch(s, f, base), reps)
+            rows.append(dict(metric="IG", H=H, W=W, nfix=nfix, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32,
                              numpy_model_ms_per_map_one_core=host * 1e3))
             print(json.dumps(rows[-1]), flush=True)
     if args.forward:

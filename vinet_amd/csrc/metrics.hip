@@ -1,4 +1,5 @@
-// The validation metrics that need more than one reduction: AUC-Judd (below) and the shuffled AUC (second half of the file).
+// The validation metrics that need more than one reduction: AUC-Judd (below), the shuffled AUC (second part of the file), and
+// AUC-Borji and the information gain (last part), which reuse the shuffled AUC's pieces.
 //
 // AUC-Judd (loss.py:122-213), the fifth validation metric, as a rank problem: one workgroup (1024 lanes) per map.
 //
@@ -270,10 +271,12 @@ VN_DEV void sauc_keys(int64_t seed, int64_t frame, int split, uint32_t* k0, uint
 }
 VN_DEV uint32_t sauc_key(uint32_t p, uint32_t k0, uint32_t k1) { return mix32(mix32(p ^ k0) + k1); }
 
+// `oth` == nullptr (AUC-Borji, below): there is no other set, M = n and no list.  `min_fix`: fewer fixations than that give NaN
+// (1 for the shuffled AUC, 2 for AUC-Borji).
 template <typename TS, bool F64>
 __global__ __launch_bounds__(AUC_LANES) void sauc_prep_kernel(const TS* __restrict__ s, const void* fix, const void* oth, int okind, long ostride,
-                                                              int n, double step, int T, int want_list, char* ws, size_t ws_per_map,
-                                                              size_t ws_list_off) {
+                                                              int n, int min_fix, double step, int T, int want_list, char* ws,
+                                                              size_t ws_per_map, size_t ws_list_off) {
   __shared__ int hst[SAUC_MAX_T + 1];
   __shared__ double sh[16];
   __shared__ int shi[16];
@@ -296,7 +299,7 @@ __global__ __launch_bounds__(AUC_LANES) void sauc_prep_kernel(const TS* __restri
     bad |= v != v;
     const bool f = ldg<F64>(fix, fb + i) > 0.0;
     cnt += f;
-    co += !f && sauc_other_on(oth, okind, ob + i);
+    co += oth && !f && sauc_other_on(oth, okind, ob + i);
   }
   mx = block_max_d(mx, sh);
   mn = -block_max_d(-mn, sh);
@@ -311,9 +314,10 @@ __global__ __launch_bounds__(AUC_LANES) void sauc_prep_kernel(const TS* __restri
     if (k < wv) base += wcnt[k];
     M += wcnt[k];
   }
+  if (!oth) M = n;
   const TS lo = (TS)mn, range = (TS)mx - (TS)mn;
-  // AUC_shuffled.m:33-36 (no fixation), :46-49 (constant map / NaN), and 0/0 of an empty other set
-  const int nan = N == 0 || nbad || !(range > (TS)0) || M == 0;
+  // AUC_shuffled.m:33-36 (no fixation; AUC_Borji.m:31 with <= 1), :46-49 (constant map / NaN), and 0/0 of an empty other set
+  const int nan = N < min_fix || nbad || !(range > (TS)0) || M == 0;
   if (tid == 0) { head->lo = (double)lo; head->range = (double)range; head->N = N; head->M = M; head->nan = nan; head->pad = 0; }
   if (nan) return;
   for (int i = tid; i <= T; i += AUC_LANES) hst[i] = 0;
@@ -334,6 +338,33 @@ __global__ __launch_bounds__(AUC_LANES) void sauc_prep_kernel(const TS* __restri
   for (int i = tid; i <= T; i += AUC_LANES) tpc[i] = hst[i];
 }
 
+// one split's locations as the caller gave them (a row of `samples`: pixel indices, then -1): their bin counts into cnt, the number
+// of valid ones into *fill.  Every lane of the group calls it; cnt and *fill were zeroed by the caller.
+template <typename TS>
+VN_DEV void sauc_given(const TS* __restrict__ sp, int n, const int32_t* row, int kmax, TS lo, TS range, double step, int T, int* cnt, int* fill) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  for (int c = 0; c < kmax; c += AUC_LANES) {
+    const int p = c + tid < kmax ? row[c + tid] : -1;
+    const bool act = p >= 0 && p < n;
+    const int j = act ? sauc_bin(auc_norm<TS>(sp[p], lo, range), step, T) : 0;
+    sauc_count(cnt, j, act, T + 1);
+    const unsigned long long m = __ballot(act);
+    if ((tid & 63) == 0 && m) atomicAdd(fill, __popcll(m));
+  }
+}
+// the area of one split from the suffix counts cnt (the locations, K of them) and tpc (the fixations, N of them):
+// points P_0 = (0,0), P_i = (fp_k, tp_k) with k = T - i for i = 1 .. T, P_{T+1} = (1,1); trapz over the T + 1 intervals
+VN_DEV double sauc_trapz(const int* cnt, const int* tpc, int T, double dK, double dN, double* sh) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i <= T; i += AUC_LANES) {
+    const double x0 = i == 0 ? 0.0 : (double)cnt[T - i + 1] / dK, y0 = i == 0 ? 0.0 : (double)tpc[T - i + 1] / dN;
+    const double x1 = i == T ? 1.0 : (double)cnt[T - i] / dK, y1 = i == T ? 1.0 : (double)tpc[T - i] / dN;
+    acc += (x1 - x0) * (y1 + y0) / 2.0;
+  }
+  return block_sum_d(acc, sh);
+}
+
 // the splits g, g + G, ... of one map on a list that lives in LDS or in the workspace (inlined once per address space)
 template <typename TS>
 VN_DEV void sauc_splits(const TS* __restrict__ sp, int n, const int* lp, int N, int M, TS lo, TS range, int nsplits, double step, int T,
@@ -346,16 +377,7 @@ VN_DEV void sauc_splits(const TS* __restrict__ sp, int n, const int* lp, int N, 
     if (tid == 0) *fill = 0;
     int32_t* out = samples_out ? samples_out + (long)sp_i * kmax : nullptr;
     if (samples) {
-      __syncthreads();
-      const int32_t* row = samples + (long)sp_i * kmax;
-      for (int c = 0; c < kmax; c += AUC_LANES) {
-        const int p = c + tid < kmax ? row[c + tid] : -1;
-        const bool act = p >= 0 && p < n;
-        const int j = act ? sauc_bin(auc_norm<TS>(sp[p], lo, range), step, T) : 0;
-        sauc_count(cnt, j, act, T + 1);
-        const unsigned long long m = __ballot(act);
-        if ((tid & 63) == 0 && m) atomicAdd(fill, __popcll(m));
-      }
+      sauc_given<TS>(sp, n, samples + (long)sp_i * kmax, kmax, lo, range, step, T, cnt, fill);
     } else {
       uint32_t k0, k1, kth = 0xffffffffu;
       sauc_keys(seed, frame, sp_i, &k0, &k1);
@@ -403,14 +425,7 @@ VN_DEV void sauc_splits(const TS* __restrict__ sp, int n, const int* lp, int N, 
     const int got = *fill;
     if (out && !samples)
       for (int i = got + tid; i < kmax; i += AUC_LANES) out[i] = -1;
-    // points P_0 = (0,0), P_i = (fp_k, tp_k) with k = T - i for i = 1 .. T, P_{T+1} = (1,1); trapz over the T + 1 intervals
-    double acc = 0.0;
-    for (int i = tid; i <= T; i += AUC_LANES) {
-      const double x0 = i == 0 ? 0.0 : (double)cnt[T - i + 1] / dK, y0 = i == 0 ? 0.0 : (double)tpc[T - i + 1] / dN;
-      const double x1 = i == T ? 1.0 : (double)cnt[T - i] / dK, y1 = i == T ? 1.0 : (double)tpc[T - i] / dN;
-      acc += (x1 - x0) * (y1 + y0) / 2.0;
-    }
-    acc = block_sum_d(acc, sh);
+    const double acc = sauc_trapz(cnt, tpc, T, dK, dN, sh);
     if (tid == 0) auc[sp_i] = got == K ? acc : NAN;
   }
 }
@@ -463,7 +478,7 @@ __global__ void sauc_mean_kernel(const char* ws, size_t ws_map0, size_t ws_per_m
   if (b >= B) return;
   const SaucHead* head = (const SaucHead*)(ws + ws_map0 + (size_t)b * ws_per_map);
   nfix[b] = head->N;
-  nother[b] = head->M;
+  if (nother) nother[b] = head->M;
   if (head->nan) { score[b] = NAN; return; }
   const double* auc = (const double*)ws + (long)b * nsplits;
   double acc = 0.0;
@@ -515,7 +530,7 @@ extern "C" int vinet_auc_shuffled(const void* s, int32_t s_is_f64, const void* f
   G = G > nsplits ? nsplits : G;
   const int want_list = samples ? 0 : 1;
 #define SAUC_PREP(TS, F64) \
-  hipLaunchKernelGGL((sauc_prep_kernel<TS, F64>), dim3(B), dim3(AUC_LANES), 0, st, (const TS*)s, fix, other, other_kind, (long)other_stride, n, step, T, want_list, ws + map0, per, loff)
+  hipLaunchKernelGGL((sauc_prep_kernel<TS, F64>), dim3(B), dim3(AUC_LANES), 0, st, (const TS*)s, fix, other, other_kind, (long)other_stride, n, 1, step, T, want_list, ws + map0, per, loff)
 #define SAUC_SPLIT(TS) \
   hipLaunchKernelGGL((sauc_split_kernel<TS>), dim3(B, G), dim3(AUC_LANES), 0, st, (const TS*)s, n, nsplits, step, T, seed, frame_ids, samples, kmax, g_vinet_opt_sauc_ws, ws, map0, per, loff, samples_out)
   if (s_is_f64) { if (fix_is_f64) SAUC_PREP(double, true); else SAUC_PREP(double, false); SAUC_SPLIT(double); }
@@ -524,4 +539,188 @@ extern "C" int vinet_auc_shuffled(const void* s, int32_t s_is_f64, const void* f
 #undef SAUC_SPLIT
   hipLaunchKernelGGL(sauc_mean_kernel, dim3((B + 63) / 64), dim3(64), 0, st, ws, map0, per, B, nsplits, score, nfix, nother);
   return vn_launch_status("auc_shuffled");
+}
+
+// ---- AUC-Borji (code_for_Metrics/AUC_Borji.m) -------------------------------------------------------------------------------------
+//
+// The shuffled AUC with another draw of the negative locations: N of them per split, uniform over ALL n pixels, with replacement
+// (AUC_Borji.m:58 `randi([1 Npixels], [Nfixations, Nsplits])`): a fixation pixel may be drawn and a pixel may repeat.  tp and fp
+// are both divided by N (:75-76), one fixation or none is NaN (:31).  The sweep `0:stepSize:max([Sth;curfix])` of :67 is the
+// shuffled AUC's "every t_k <= 1" for the same reason: a threshold above every value gives the point (0, 0) again, zero area.
+// Three launches: sauc_prep_kernel without an other map (min / max / N and the fixations' suffix counts, once per map),
+// borji_split_kernel over (map, split group), sauc_mean_kernel.  There is no list and no select: sample j of split q is pixel
+// ((uint64)h * n) >> 32 with h = sauc_key(j, k0, k1), (k0, k1) = sauc_keys(seed ^ BORJI_DOMAIN, frame id, q) -- a function of
+// (seed, frame id, split, j) alone, and not the stream the shuffled AUC draws from under the same seed.
+#define BORJI_DOMAIN 0x426f726a69415543ll          // "BorjiAUC"
+
+template <typename TS>
+__global__ __launch_bounds__(AUC_LANES) void borji_split_kernel(const TS* __restrict__ s, int n, int nsplits, double step, int T, int64_t seed,
+                                                                const int64_t* frame_ids, const int32_t* samples, int kmax, char* ws,
+                                                                size_t ws_map0, size_t ws_per_map, int32_t* samples_out) {
+  __shared__ int tpc[SAUC_MAX_T + 1];
+  __shared__ int cnt[SAUC_MAX_T + 1];
+  __shared__ double sh[16];
+  __shared__ int shi[16];
+  __shared__ int fill;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const char* wm = ws + ws_map0 + (size_t)b * ws_per_map;
+  const SaucHead* head = (const SaucHead*)wm;
+  int32_t* outb = samples_out ? samples_out + (long)b * nsplits * kmax : nullptr;
+  if (head->nan) {                               // sauc_mean_kernel writes the NaN; the sample rows of such a map are empty
+    if (outb)
+      for (int sp_i = blockIdx.y; sp_i < nsplits; sp_i += gridDim.y)
+        for (int i = tid; i < kmax; i += AUC_LANES) outb[(long)sp_i * kmax + i] = -1;
+    return;
+  }
+  const int N = head->N;
+  const TS lo = (TS)head->lo, range = (TS)head->range;
+  const int* tp_ws = (const int*)(wm + sizeof(SaucHead));
+  for (int i = tid; i <= T; i += AUC_LANES) tpc[i] = tp_ws[i];
+  const int64_t frame = frame_ids ? frame_ids[b] : (int64_t)b;
+  const int32_t* smp = samples ? samples + (long)b * nsplits * kmax : nullptr;
+  double* auc = (double*)ws + (long)b * nsplits;
+  const TS* sp = s + (long)b * n;
+  const double dN = (double)N;
+  for (int sp_i = blockIdx.y; sp_i < nsplits; sp_i += gridDim.y) {
+    for (int i = tid; i <= T; i += AUC_LANES) cnt[i] = 0;
+    if (tid == 0) fill = 0;
+    int32_t* out = outb ? outb + (long)sp_i * kmax : nullptr;
+    if (smp) {
+      sauc_given<TS>(sp, n, smp + (long)sp_i * kmax, kmax, lo, range, step, T, cnt, &fill);
+    } else {
+      uint32_t k0, k1;
+      sauc_keys(seed ^ BORJI_DOMAIN, frame, sp_i, &k0, &k1);
+      __syncthreads();
+      for (int c = 0; c < N; c += AUC_LANES) {
+        const int j = c + tid;
+        const bool act = j < N;
+        const int p = act ? (int)(((uint64_t)sauc_key((uint32_t)j, k0, k1) * (uint64_t)(uint32_t)n) >> 32) : 0;      // in [0, n)
+        const int bin = act ? sauc_bin(auc_norm<TS>(sp[p], lo, range), step, T) : 0;
+        sauc_count(cnt, bin, act, T + 1);
+        if (out && act && j < kmax) out[j] = p;
+      }
+      if (tid == 0) fill = N;
+    }
+    sauc_suffix(cnt, T + 1, shi);                 // cnt[j] = #{ curfix in bin >= j }; fill = the locations counted
+    const int got = fill;
+    if (out && !smp)
+      for (int i = N + tid; i < kmax; i += AUC_LANES) out[i] = -1;
+    const double acc = sauc_trapz(cnt, tpc, T, dN, dN, sh);
+    if (tid == 0) auc[sp_i] = got == N ? acc : NAN;
+  }
+}
+
+extern "C" size_t vinet_auc_borji_workspace(int32_t B, int32_t n, int32_t nsplits, double step) {
+  const int T = sauc_thresholds(step);
+  if (B <= 0 || n <= 0 || n > (1 << 30) || nsplits <= 0 || T == 0) return 0;
+  return (size_t)B * nsplits * sizeof(double) + (size_t)B * sauc_list_off(T);
+}
+
+extern "C" int vinet_auc_borji(const void* s, int32_t s_is_f64, const void* fix, int32_t fix_is_f64, int32_t B, int32_t n, int32_t nsplits,
+                               double step, int64_t seed, const int64_t* frame_ids, const int32_t* samples, int32_t kmax, void* workspace,
+                               size_t workspace_bytes, double* score, int32_t* nfix, int32_t* samples_out, void* stream) {
+  VN_CHECK_ARG(s && fix && score && nfix, "auc_borji: null map, fixation map, score or nfix");
+  VN_CHECK_ARG(B > 0 && n > 0 && n <= (1 << 30) && nsplits > 0, "auc_borji: B, n and nsplits must be positive (n <= 2^30)");
+  VN_CHECK_ARG(step > 0.0 && step <= 1.0, "auc_borji: step must lie in (0, 1]");
+  const int T = sauc_thresholds(step);
+  VN_CHECK_ARG(T > 0, "auc_borji: step %g gives more than %d thresholds", step, SAUC_MAX_T);
+  VN_CHECK_ARG((!samples && !samples_out) || kmax > 0, "auc_borji: kmax must be positive with samples or samples_out");
+  VN_CHECK_ARG(!(samples && samples_out), "auc_borji: samples_out returns the device draw; the given samples are the caller's already");
+  const size_t need = vinet_auc_borji_workspace(B, n, nsplits, step);
+  VN_CHECK_ARG(workspace && workspace_bytes >= need && (((uintptr_t)workspace) & 7) == 0,
+               "auc_borji: workspace of %zu bytes (8-byte aligned) needed, got %zu", need, workspace ? workspace_bytes : (size_t)0);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t map0 = (size_t)B * nsplits * sizeof(double), per = sauc_list_off(T);
+  char* ws = (char*)workspace;
+  // split groups per map as for the shuffled AUC; the result does not depend on it
+  int G = 2048 / B;
+  G = G < 1 ? 1 : (G > 32 ? 32 : G);
+  G = G > nsplits ? nsplits : G;
+#define BORJI_PREP(TS, F64) \
+  hipLaunchKernelGGL((sauc_prep_kernel<TS, F64>), dim3(B), dim3(AUC_LANES), 0, st, (const TS*)s, fix, nullptr, 0, 0l, n, 2, step, T, 0, ws + map0, per, per)
+#define BORJI_SPLIT(TS) \
+  hipLaunchKernelGGL((borji_split_kernel<TS>), dim3(B, G), dim3(AUC_LANES), 0, st, (const TS*)s, n, nsplits, step, T, seed, frame_ids, samples, kmax, ws, map0, per, samples_out)
+  if (s_is_f64) { if (fix_is_f64) BORJI_PREP(double, true); else BORJI_PREP(double, false); BORJI_SPLIT(double); }
+  else { if (fix_is_f64) BORJI_PREP(float, true); else BORJI_PREP(float, false); BORJI_SPLIT(float); }
+#undef BORJI_PREP
+#undef BORJI_SPLIT
+  hipLaunchKernelGGL(sauc_mean_kernel, dim3((B + 63) / 64), dim3(64), 0, st, ws, map0, per, B, nsplits, score, nfix, (int*)nullptr);
+  return vn_launch_status("auc_borji");
+}
+
+// ---- information gain (code_for_Metrics/InfoGain.m, IG.m) ---------------------------------------------------------------------------
+//
+// Per map, everything in fp64 on the input values: v = (s - min) / (max - min) (InfoGain.m:17, IG.m:13), p = v / sum(v)
+// (InfoGain.m:22, IG.m:17), the same for the baseline map (InfoGain.m:18,23; IG.m:21-23), and
+// score = mean over the fixations of log2(eps + p) - log2(eps + pb), eps = 2^-52 (InfoGain.m:27, IG.m:25,35); without a baseline
+// the second term is absent (IG.m:28-31).  A fixation is `fix > 0` as everywhere in this library (the .m files take
+// logical(fixationMap); fixation maps are non-negative).  One workgroup per map, three passes: min / max / NaN / N, the two sums,
+// the fixations; every reduction is per-lane strided partial results through the fixed block tree: two runs agree bit for bit
+// and a map's score does not depend on the batch.  NaN: no fixation (the mean of nothing), a constant map or baseline (0/0
+// everywhere), a NaN in either.
+VN_DEV double ig_ld(const void* p, int is64, long i) { return is64 ? ((const double*)p)[i] : (double)((const float*)p)[i]; }
+
+__global__ __launch_bounds__(AUC_LANES) void info_gain_kernel(const void* __restrict__ s, int s64, const void* __restrict__ fix, int f64,
+                                                              const void* __restrict__ base, int b64, long bstride, int n,
+                                                              double* __restrict__ score, int* __restrict__ nfix) {
+  __shared__ double sh[16];
+  __shared__ int shi[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long sb = (long)b * n, bb = (long)b * bstride;
+  double mn = INFINITY, mx = -INFINITY, mnb = INFINITY, mxb = -INFINITY;
+  int cnt = 0, bad = 0;
+  for (int i = tid; i < n; i += AUC_LANES) {
+    const double v = ig_ld(s, s64, sb + i);
+    mn = fmin(mn, v); mx = fmax(mx, v);
+    bad |= v != v;
+    cnt += ig_ld(fix, f64, sb + i) > 0.0;
+    if (base) {
+      const double w = ig_ld(base, b64, bb + i);
+      mnb = fmin(mnb, w); mxb = fmax(mxb, w);
+      bad |= w != w;
+    }
+  }
+  mx = block_max_d(mx, sh);
+  mn = -block_max_d(-mn, sh);
+  if (base) {
+    mxb = block_max_d(mxb, sh);
+    mnb = -block_max_d(-mnb, sh);
+  }
+  int N, nbad;
+  block_excl_scan_i(cnt, shi, &N);
+  block_excl_scan_i(bad, shi, &nbad);
+  const double range = mx - mn, rangeb = mxb - mnb;
+  if (tid == 0) nfix[b] = N;
+  if (N == 0 || nbad || !(range > 0.0) || (base && !(rangeb > 0.0))) {
+    if (tid == 0) score[b] = NAN;
+    return;
+  }
+  double sum = 0.0, sumb = 0.0;
+  for (int i = tid; i < n; i += AUC_LANES) {
+    sum += (ig_ld(s, s64, sb + i) - mn) / range;
+    if (base) sumb += (ig_ld(base, b64, bb + i) - mnb) / rangeb;
+  }
+  sum = block_sum_d(sum, sh);
+  if (base) sumb = block_sum_d(sumb, sh);
+  const double eps = 2.220446049250313e-16;       // MATLAB's eps = 2^-52
+  double acc = 0.0;
+  for (int i = tid; i < n; i += AUC_LANES)
+    if (ig_ld(fix, f64, sb + i) > 0.0) {
+      double t = log2(eps + (ig_ld(s, s64, sb + i) - mn) / range / sum);
+      if (base) t -= log2(eps + (ig_ld(base, b64, bb + i) - mnb) / rangeb / sumb);
+      acc += t;
+    }
+  acc = block_sum_d(acc, sh);
+  if (tid == 0) score[b] = acc / (double)N;
+}
+
+extern "C" int vinet_info_gain(const void* s, int32_t s_is_f64, const void* fix, int32_t fix_is_f64, const void* baseline,
+                               int32_t baseline_is_f64, int64_t baseline_stride, int32_t B, int32_t n, double* score, int32_t* nfix,
+                               void* stream) {
+  VN_CHECK_ARG(s && fix && score && nfix, "info_gain: null map, fixation map, score or nfix");
+  VN_CHECK_ARG(B > 0 && n > 0 && n <= (1 << 30), "info_gain: B and n must be positive (n <= 2^30)");
+  VN_CHECK_ARG(baseline_stride == 0 || baseline_stride >= n, "info_gain: baseline_stride is 0 (one map for the batch) or >= n");
+  hipLaunchKernelGGL(info_gain_kernel, dim3(B), dim3(AUC_LANES), 0, (hipStream_t)stream, s, s_is_f64 ? 1 : 0, fix, fix_is_f64 ? 1 : 0, baseline,
+                     baseline_is_f64 ? 1 : 0, (long)baseline_stride, n, score, nfix);
+  return vn_launch_status("info_gain");
 }

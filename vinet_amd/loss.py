@@ -13,6 +13,8 @@ integer counts).  `auc_shuff` (loss.py:215-284) is left out on purpose: the refe
 (it calls the torch `normalize_map` on a numpy array), so there is nothing to reproduce.  The shuffled AUC that the
 reference's evaluation does compute is the MATLAB one (code_for_Metrics/AUC_shuffled.m, called from eval_diem.m): that is
 `auc_shuffled` / `auc_shuffled_batch` here (libvinet_hip.so: vinet_auc_shuffled), with `shuffle_map` for createShuffmap1.m.
+The two other fixation metrics of that folder run on the device as well: `auc_borji` / `auc_borji_batch` (AUC_Borji.m;
+vinet_auc_borji) and `info_gain` / `info_gain_batch` (InfoGain.m, IG.m; vinet_info_gain).
 """
 import torch
 
@@ -216,9 +218,7 @@ def auc_shuffled_batch(s_maps, fix_maps, other_map, *, n_splits=100, step=0.1, s
                                    E._stream_for(dev)), "vinet_auc_shuffled")
     if return_samples:
         # the kernel fills a row in no particular order: ascending, the -1 padding last
-        big = torch.iinfo(torch.int32).max
-        srt = torch.where(out < 0, torch.full_like(out, big), out).sort(dim=2).values
-        return score, nfix, nother, torch.where(srt == big, torch.full_like(srt, -1), srt)
+        return score, nfix, nother, _sorted_samples(out)
     return (score, nfix, nother) if return_counts else score
 
 
@@ -236,6 +236,128 @@ def auc_shuffled(saliencyMap, fixationMap, otherMap, Nsplits=100, stepSize=0.1):
     if score != score:
         print('no fixationMap' if nfix == 0 else 'NaN saliencyMap')
     return score
+
+
+def _sorted_samples(out):
+    """sample rows ascending, the -1 padding last"""
+    big = torch.iinfo(torch.int32).max
+    srt = torch.where(out < 0, torch.full_like(out, big), out).sort(dim=2).values
+    return torch.where(srt == big, torch.full_like(srt, -1), srt)
+
+
+@torch.no_grad()
+def auc_borji_batch(s_maps, fix_maps, *, n_splits=100, step=0.1, seed=0, frame_ids=None, samples=None, return_samples=False,
+                    return_counts=False):
+    """AUC-Borji (AUC_Borji.m) of every map of a batch: `[B,H,W]` float32 or float64 saliency maps, fixation maps of the same
+    size -> float64 `[B]` on the device.  Per split N = #fixations locations drawn from ALL pixels, uniformly and with
+    replacement (MATLAB's randi); tp and fp over N; NaN where a map has at most one fixation (AUC_Borji.m:31), is constant or
+    holds a NaN.
+    The locations are drawn on the device as a function of (`seed`, the map's frame id, split, sample number) -- `frame_ids`:
+    int64 `[B]`, default 0 .. B-1; a map's score does not depend on the batch around it; the stream is not the one
+    `auc_shuffled_batch` draws from under the same seed -- or taken from `samples`: int32 `[B, n_splits, kmax]`, each row N
+    pixel indices then -1.
+    `return_counts`: also the fixations `[B]` (int32); `return_samples`: those and the drawn locations, int32
+    `[B, n_splits, max N]`, each row ascending and padded with -1."""
+    assert s_maps.size() == fix_maps.size(), "auc_borji: resize the saliency map to the fixation map first"
+    assert s_maps.dim() == 3, "expected [B,H,W] maps"
+    assert samples is None or not return_samples, "return_samples returns the device draw"
+    s = s_maps.detach()
+    if s.dtype not in (torch.float32, torch.float64):
+        s = s.float()
+    s = s.contiguous()
+    g = _fix_maps(fix_maps)
+    if g.device != s.device:
+        raise ValueError("auc_borji: fix_maps on %s, the maps on %s" % (g.device, s.device))
+    B, n = s.shape[0], s.shape[1] * s.shape[2]
+    dev = s.device
+    lib = L.get()
+    fid = None
+    if frame_ids is not None:
+        fid = torch.as_tensor(frame_ids, dtype=torch.int64).to(dev).contiguous()
+        assert tuple(fid.shape) == (B,), "frame_ids: one int64 per map"
+    smp = out = None
+    kmax = 0
+    if samples is not None:
+        assert samples.dim() == 3 and tuple(samples.shape[:2]) == (B, n_splits) and samples.shape[2] > 0, "samples: [B, n_splits, kmax]"
+        smp = samples.detach().to(device=dev, dtype=torch.int32).contiguous()
+        kmax = smp.shape[2]
+    elif return_samples:
+        kmax = max(int((g > 0).flatten(1).sum(1).max()), 1)
+        out = torch.empty((B, n_splits, kmax), dtype=torch.int32, device=dev)
+    need = int(lib.vinet_auc_borji_workspace(B, n, int(n_splits), float(step)))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    score = torch.empty(B, dtype=torch.float64, device=dev)
+    nfix = torch.empty(B, dtype=torch.int32, device=dev)
+    L.check(lib.vinet_auc_borji(s.data_ptr(), 1 if s.dtype == torch.float64 else 0, g.data_ptr(), 1 if g.dtype == torch.float64 else 0,
+                                B, n, int(n_splits), float(step), int(seed), fid.data_ptr() if fid is not None else None,
+                                smp.data_ptr() if smp is not None else None, kmax, ws.data_ptr(), need, score.data_ptr(),
+                                nfix.data_ptr(), out.data_ptr() if out is not None else None, E._stream_for(dev)), "vinet_auc_borji")
+    if return_samples:
+        return score, nfix, _sorted_samples(out)
+    return (score, nfix) if return_counts else score
+
+
+def auc_borji(saliencyMap, fixationMap, Nsplits=100, stepSize=0.1):
+    """AUC_Borji.m's signature for maps of equal size (2-D, or item 0 of a 3-D batch as `auc_judd` takes it) -> Python float.
+    Prints the MATLAB messages and returns NaN when there is at most one fixation (AUC_Borji.m:31-35) or the map is constant
+    (:45-48); toPlot has no counterpart."""
+    assert saliencyMap.size() == fixationMap.size(), "auc_borji: resize the saliency map to the fixation map first"
+    assert saliencyMap.dim() in (2, 3), "expected a [H,W] map or a [B,H,W] batch"
+    s = saliencyMap[:1] if saliencyMap.dim() == 3 else saliencyMap.unsqueeze(0)
+    f = fixationMap[:1] if fixationMap.dim() == 3 else fixationMap.unsqueeze(0)
+    score, nfix = auc_borji_batch(s, f, n_splits=Nsplits, step=stepSize, return_counts=True)
+    score, nfix = float(score[0]), int(nfix[0])
+    if score != score:
+        print('no fixationMap' if nfix <= 1 else 'NaN saliencyMap')
+    return score
+
+
+@torch.no_grad()
+def info_gain_batch(s_maps, fix_maps, baseline=None, *, return_counts=False):
+    """Information gain (InfoGain.m; IG.m without a baseline) of every map of a batch: `[B,H,W]` float32 or float64 saliency
+    maps, fixation maps of the same size, `baseline` None, `[H,W]` (one for the batch) or `[B,H,W]`, float32 or float64 ->
+    float64 `[B]` on the device: the mean over the fixations of log2(eps + p) - log2(eps + pb), p and pb the min-max normalised
+    maps divided by their sums, all in float64.  NaN where a map has no fixation, the map or its baseline is constant, or
+    either holds a NaN.  `return_counts`: also the fixations `[B]` (int32)."""
+    assert s_maps.size() == fix_maps.size(), "info_gain: resize the saliency map to the fixation map first"
+    assert s_maps.dim() == 3, "expected [B,H,W] maps"
+    s = s_maps.detach()
+    if s.dtype not in (torch.float32, torch.float64):
+        s = s.float()
+    s = s.contiguous()
+    g = _fix_maps(fix_maps)
+    if g.device != s.device:
+        raise ValueError("info_gain: fix_maps on %s, the maps on %s" % (g.device, s.device))
+    B, n = s.shape[0], s.shape[1] * s.shape[2]
+    dev = s.device
+    bl = None
+    if baseline is not None:
+        assert baseline.dim() in (2, 3) and tuple(baseline.shape[-2:]) == tuple(s.shape[1:]), "baseline: [H,W] or [B,H,W] of the maps' size"
+        assert baseline.dim() == 2 or baseline.shape[0] == B, "baseline: one map, or one per saliency map"
+        bl = baseline.detach()
+        if bl.dtype not in (torch.float32, torch.float64):
+            bl = bl.float()
+        bl = bl.contiguous()
+        if bl.device != dev:
+            raise ValueError("info_gain: baseline on %s, the maps on %s" % (bl.device, dev))
+    score = torch.empty(B, dtype=torch.float64, device=dev)
+    nfix = torch.empty(B, dtype=torch.int32, device=dev)
+    L.check(L.get().vinet_info_gain(s.data_ptr(), 1 if s.dtype == torch.float64 else 0, g.data_ptr(), 1 if g.dtype == torch.float64 else 0,
+                                    bl.data_ptr() if bl is not None else None, 1 if bl is not None and bl.dtype == torch.float64 else 0,
+                                    0 if bl is None or bl.dim() == 2 else n, B, n, score.data_ptr(), nfix.data_ptr(),
+                                    E._stream_for(dev)), "vinet_info_gain")
+    return (score, nfix) if return_counts else score
+
+
+def info_gain(saliencyMap, fixationMap, baselineMap=None):
+    """InfoGain.m's signature (IG.m's when `baselineMap` is None) for maps of equal size (2-D, or item 0 of a 3-D batch) ->
+    Python float."""
+    assert saliencyMap.size() == fixationMap.size(), "info_gain: resize the saliency map to the fixation map first"
+    assert saliencyMap.dim() in (2, 3), "expected a [H,W] map or a [B,H,W] batch"
+    s = saliencyMap[:1] if saliencyMap.dim() == 3 else saliencyMap.unsqueeze(0)
+    f = fixationMap[:1] if fixationMap.dim() == 3 else fixationMap.unsqueeze(0)
+    bl = None if baselineMap is None else (baselineMap[0] if baselineMap.dim() == 3 else baselineMap)
+    return float(info_gain_batch(s, f, bl)[0])
 
 
 @torch.no_grad()

@@ -17,6 +17,8 @@ weights and biases are fp32 in torch's own layout (`[N, Cin, kT, kH, kW]`), exac
     torch.ops.vinet.saliency_loss / saliency_loss_bwd                    kldiv / cc / similarity          loss.py:13-99
     torch.ops.vinet.auc_judd(s_maps, fix_maps, mit)                      AUC-Judd per map (forward only)  loss.py:122-213
     torch.ops.vinet.auc_shuffled(s_maps, fix_maps, other_map, n_splits, step, seed, frame_ids)   s-AUC per map   AUC_shuffled.m
+    torch.ops.vinet.auc_borji(s_maps, fix_maps, n_splits, step, seed, frame_ids)                 AUC-Borji per map   AUC_Borji.m
+    torch.ops.vinet.info_gain(s_maps, fix_maps, baseline)                                        information gain per map   InfoGain.m, IG.m
     torch.ops.vinet.adam_step_                                           torch.optim.Adam.step over a flat buffer   train.py:188,217
 
 There is no CPU kernel behind them: on a CPU tensor they raise (vinet_amd._lib), except under the tests' ABI double.
@@ -315,6 +317,31 @@ def auc_shuffled(s_maps: Tensor, fix_maps: Tensor, other_map: Tensor, n_splits: 
 
 @auc_shuffled.register_fake
 def _(s_maps, fix_maps, other_map, n_splits, step, seed, frame_ids):
+    return s_maps.new_empty((s_maps.shape[0],), dtype=torch.float64)
+
+
+# ---- AUC-Borji and information gain (validation metrics: no autograd) ----------------------------------------------------------------
+@torch.library.custom_op("vinet::auc_borji", mutates_args=())
+def auc_borji(s_maps: Tensor, fix_maps: Tensor, n_splits: int, step: float, seed: int, frame_ids: Optional[Tensor]) -> Tensor:
+    """[B,H,W] saliency and fixation maps -> fp64 [B] scores of the device draw, NaN allowed"""
+    from . import loss as VL
+    return VL.auc_borji_batch(s_maps, fix_maps, n_splits=n_splits, step=step, seed=seed, frame_ids=frame_ids)
+
+
+@auc_borji.register_fake
+def _(s_maps, fix_maps, n_splits, step, seed, frame_ids):
+    return s_maps.new_empty((s_maps.shape[0],), dtype=torch.float64)
+
+
+@torch.library.custom_op("vinet::info_gain", mutates_args=())
+def info_gain(s_maps: Tensor, fix_maps: Tensor, baseline: Optional[Tensor]) -> Tensor:
+    """[B,H,W] saliency and fixation maps, a baseline map [H,W] or [B,H,W] or None -> fp64 [B] scores, NaN allowed"""
+    from . import loss as VL
+    return VL.info_gain_batch(s_maps, fix_maps, baseline)
+
+
+@info_gain.register_fake
+def _(s_maps, fix_maps, baseline):
     return s_maps.new_empty((s_maps.shape[0],), dtype=torch.float64)
 
 
