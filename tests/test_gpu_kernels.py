@@ -636,7 +636,18 @@ def test_conv3d_tstream_dgrad_phase(r):
     _cmp(yp.get("gpu"), yp.get("cpu"), TOL[dt], "temporal dgrad phase")
 
 
-def _run_conv_case(case, dt, forced=False, want_y=False, cdt=None, tol=None):
+def _pre_affine(pre, scale, shift, side):
+    """ex["pre"]: True = BatchNorm + ReLU (scale, shift, relu); "affine" = scale + shift without ReLU; "relu" = ReLU alone"""
+    if pre == "relu":
+        return L.CAffine(None, None, 1)
+    if pre:
+        return L.CAffine(scale.ptr(side), shift.ptr(side), 0 if pre == "affine" else 1)
+    return L.CAffine(None, None, 0)
+
+
+def _run_conv_case(case, dt, forced=False, want_y=False, cdt=None, tol=None, hook=None):
+    """hook(ns): called after every check with the case's tensors still alive (ns: mk, xp, yp, y_init, wp, taps, the extents) --
+    tests/test_gpu_routes.py compares against altered references and re-launches under other options through it"""
     name, (B, T, H, W), Cin, N, k, s, p, ex = case
     oT, oH, oW = [(d + 2 * pp - kk) // ss + 1 for d, kk, ss, pp in zip((T, H, W), k, s, p)]
     xp, xmk = view_pair(B, T, H, W, Cin, dt, "x" + name, 1, t_total=ex.get("in_ttotal"), t_off=ex.get("in_toff", 0),
@@ -647,6 +658,7 @@ def _run_conv_case(case, dt, forced=False, want_y=False, cdt=None, tol=None):
     omT, ooT = ex.get("om", (1, 0))
     yp, ymk = view_pair(B, oT * omT, oH, oW, Ny, odt, "y" + name, 2, ld=ex.get("out_ld"), c_off=ex.get("out_coff", 0),
                         t_total=ex.get("out_ttotal"), t_off=ex.get("out_toff", 0))
+    y_init = yp.cpu.clone() if hook else None
     Kp = E.rup(Cin, 32)
     ntaps = k[0] * k[1] * k[2]
     wmaster = _rand("w" + name, (N, Cin, ntaps), 3, 1.0 / math.sqrt(Cin * ntaps))
@@ -670,7 +682,7 @@ def _run_conv_case(case, dt, forced=False, want_y=False, cdt=None, tol=None):
         b_mu, b_is = fvec("bmu" + name, N, 14), fvec("bis" + name, N, 15, 0.5, 2.0)
         bpart = Pair(torch.full((rows * 2 * N,), float("nan")))
 
-    def mk(side):
+    def mk(side):      # (tests/route_cases.py::conv_desc mirrors this without tensors: change them together)
         d = L.CConvDesc()
         d.dtype, d.out_dtype, d.mode = (dt if cdt is None else cdt), odt, 0
         d.x, d.y = xmk(side).ct(), ymk(side).ct()
@@ -678,7 +690,7 @@ def _run_conv_case(case, dt, forced=False, want_y=False, cdt=None, tol=None):
         d.sT, d.sH, d.sW = s
         d.omT = d.omH = d.omW = 1
         d.ntaps, d.taps, d.w, d.Kp = ntaps, taps.ptr(side), wp.ptr(side), Kp
-        d.pre = L.CAffine(pre_s.ptr(side), pre_h.ptr(side), 1) if ex.get("pre") else L.CAffine(None, None, 0)
+        d.pre = _pre_affine(ex.get("pre"), pre_s, pre_h, side)
         d.out_scale = os_.ptr(side) if ex.get("epi") else None
         d.out_shift = oh_.ptr(side) if (ex.get("epi") or ex.get("epi_shift")) else None
         d.act = ex.get("act", 0)
@@ -742,6 +754,10 @@ def _run_conv_case(case, dt, forced=False, want_y=False, cdt=None, tol=None):
         sg = stats.get("gpu")[:r * 2 * N].view(r, 2, N).double().sum(0)
         sc = stats.get("cpu")[:rc * 2 * N].view(rc, 2, N).double().sum(0)
         _cmp(sg, sc, 1e-4 if dt == E.F32 else 2e-2, "conv stats " + name)
+    if hook:
+        hook(dict(name=name, mk=mk, xp=xp, yp=yp, ymk=ymk, y_init=y_init, wp=wp, taps=taps, stats=stats, M=M, N=N, Ny=Ny, Kp=Kp, ntaps=ntaps,
+                  dims=(B, oT, oH, oW), om=(omT, ooT), odt=odt, dt=dt, tol=TOL[dt] if tol is None else tol,
+                  bpart=bpart if bnb is not None else None))
     if want_y:
         return yp.get("gpu").clone()
     return mk("gpu")[0]._obj
@@ -1144,7 +1160,8 @@ def test_conv3d_wgrad_tframes(case):
         lib.vinet_set_option(b"wgrad_tf", 1)
 
 
-def _run_wgrad_case(case, dt, cdt=None):
+def _run_wgrad_case(case, dt, cdt=None, hook=None):
+    """ex["max_cus"]: VinetWgradDesc::max_cus; hook(ns): as _run_conv_case's"""
     name, (B, T, H, W), Cin, N, k, s, p, pre = case[:8]
     ex = case[8] if len(case) > 8 else {}
     oT, oH, oW = [(d + 2 * pp - kk) // ss + 1 for d, kk, ss, pp in zip((T, H, W), k, s, p)]
@@ -1156,19 +1173,23 @@ def _run_wgrad_case(case, dt, cdt=None):
     taps = Pair(torch.tensor(_fwd_taps(k, p), dtype=torch.int32))
     ps, ph = fvec("wps" + name, Cin, 4, 0.5, 1.5), fvec("wph" + name, Cin, 5)
 
-    def mk(side):
+    def mk(side):      # (tests/route_cases.py::wgrad_desc mirrors this without tensors: change them together)
         d = L.CWgradDesc()
         d.dtype, d.mode = (dt if cdt is None else cdt), 0
         d.x, d.dy = xmk(side).ct(), dmk(side).ct()
         d.sT, d.sH, d.sW = s
         d.ntaps, d.taps, d.dw, d.Kp = ntaps, taps.ptr(side), dw.ptr(side), Kp
-        d.pre = L.CAffine(ps.ptr(side), ph.ptr(side), 1) if pre else L.CAffine(None, None, 0)
+        d.pre = _pre_affine(pre, ps, ph, side)
         if ex.get("tline"):
             d.tline, d.tpad = (1 if ex["tline"] is True else ex["tline"]), p[0]
+        d.max_cus = ex.get("max_cus", 0)
         return [C.byref(d), _stream() if side == "gpu" else 0]
 
+    wtol = (3e-5 if cdt is None else 2e-4) if dt == E.F32 else 2e-2
     run_both("vinet_conv3d_wgrad", mk)
-    _cmp(dw.get("gpu"), dw.get("cpu"), (3e-5 if cdt is None else 2e-4) if dt == E.F32 else 2e-2, "wgrad " + name)
+    _cmp(dw.get("gpu"), dw.get("cpu"), wtol, "wgrad " + name)
+    if hook:
+        hook(dict(name=name, mk=mk, xp=xp, dp=dp, dw=dw, taps=taps, N=N, Kp=Kp, ntaps=ntaps, M=B * oT * oH * oW, tol=wtol))
     return mk("gpu")[0]._obj
 
 

@@ -65,9 +65,10 @@ for r in rows:
     k = re.sub(r"^channel_reduce8_kernel<\w+,1>$", "vinet_bn_bwd_reduce", k)
     k = re.sub(r"^bn_bwd_apply8_kernel<\w+>$", "vinet_bn_bwd_apply", k)
     # row-streaming weight gradients: the library names them by image width (vinet_conv3d_wgrad_kernel_name)
-    k = {"conv_wgrad_rsm_kernel<3,48>": "conv_wgrad_rs_kernel<W48>", "conv_wgrad_rsm_kernel<3,24>": "conv_wgrad_rs_kernel<W24>",
-         "conv_wgrad_rs_kernel<3>": "conv_wgrad_rs_kernel<W96>", "conv_wgrad_rs_kernel<6>": "conv_wgrad_rs_kernel<W192>",
-         "conv_wgrad_rs_kernel<2>": "conv_wgrad_rs_kernel<W64>", "conv_wgrad_rs_kernel<1>": "conv_wgrad_rs_kernel<W32>"}.get(k, k)
+    k = {"conv_wgrad_rsm_kernel<3,48>": "conv_wgrad_rs_kernel<W48,8w>", "conv_wgrad_rsm_kernel<3,24>": "conv_wgrad_rs_kernel<W24,8w>",
+         "conv_wgrad_rs_kernel<3>": "conv_wgrad_rs_kernel<W96,8w>", "conv_wgrad_rs_kernel<6>": "conv_wgrad_rs_kernel<W192,8w>",
+         "conv_wgrad_rs_kernel<2>": "conv_wgrad_rs_kernel<W64,8w>", "conv_wgrad_rs_kernel<1>": "conv_wgrad_rs_kernel<W32,8w>"}.get(k, k)
+    k = re.sub(r"^conv_wgrad_rs4_kernel<\d+,(\d+)>$", r"conv_wgrad_rs_kernel<W\1,4w>", k)
     k = re.sub(r"^bn_bwd_reduce8_bf16_kernel<\d+(,\d+)?>$", "vinet_bn_bwd_reduce", k)
     k = re.sub(r"^bn_bwd_apply8_bf16_kernel<\d+(,\d+)?>$", "vinet_bn_bwd_apply", k)
     m = re.match(r"conv_pw_kernel<(\d+),(\w+)>", k)       # the library names the pointwise kernel by its column-tile width

@@ -53,6 +53,7 @@ int vinet_launch_conv_tsd(const VinetConvDesc* d, hipStream_t s);
 bool vinet_wgrad_use_skinny(const VinetWgradDesc* d);
 int vinet_launch_wgrad_skinny(const VinetWgradDesc* d, hipStream_t s);
 bool vinet_wgrad_use_rs(const VinetWgradDesc* d);
+bool vinet_wgrad_rs_four_wave(const VinetWgradDesc* d);
 int vinet_launch_wgrad_rs(const VinetWgradDesc* d, hipStream_t s);
 bool vinet_wgrad_use_hs(const VinetWgradDesc* d);
 int vinet_launch_wgrad_hs(const VinetWgradDesc* d, hipStream_t s);

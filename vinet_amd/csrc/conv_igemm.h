@@ -662,12 +662,12 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
         if (ok) {
           const long off = a_base[i] + ((long)(ti * a.Hi + hi) * a.Wi + wi) * (long)a.ldx + c;
           v = *(const uint4*)(a.x + off * (long)sizeof(T));
-          if (has_pre) {
+          if (has_pre || a.in_relu) {      // (a pending ReLU without an affine -- scale == NULL: identity -- is still a ReLU)
             float f[EG];
             unpack16<T>(v, f);
 #pragma unroll
             for (int e = 0; e < EG; ++e) {
-              f[e] = fmaf(f[e], sc[e], sh[e]);
+              if (has_pre) f[e] = fmaf(f[e], sc[e], sh[e]);
               if (a.in_relu) f[e] = fmaxf(f[e], 0.f);
             }
             v = pack16<T>(f);

@@ -84,12 +84,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradArgs a) {
               (unsigned)wi < (unsigned)a.Wi) {
             const long off = (long)b * a.sBx + ((long)(ti * a.Hi + hi) * a.Wi + wi) * (long)a.ldx + c;
             vx = *(const uint4*)(a.x + off * (long)sizeof(T));
-            if (has_pre) {
+            if (has_pre || a.in_relu) {      // (a pending ReLU without an affine -- scale == NULL: identity -- is still a ReLU)
               float f[EG];
               unpack16<T>(vx, f);
 #pragma unroll
               for (int e = 0; e < EG; ++e) {
-                f[e] = fmaf(f[e], a.in_scale[c + e], a.in_shift[c + e]);
+                if (has_pre) f[e] = fmaf(f[e], a.in_scale[c + e], a.in_shift[c + e]);
                 if (a.in_relu) f[e] = fmaxf(f[e], 0.f);
               }
               vx = pack16<T>(f);
@@ -291,7 +291,7 @@ extern "C" int vinet_conv3d_wgrad_kernel_name(const VinetWgradDesc* d, char* buf
   const char* pre = d->pre.scale ? "pre" : "plain";
   switch (vinet_wgrad_route(d).kind) {
     case WGRAD_SKINNY: snprintf(buf, n, "wgrad_skinny_kernel"); break;
-    case WGRAD_RS: snprintf(buf, n, "conv_wgrad_rs_kernel<W%d>", d->dy.W); break;
+    case WGRAD_RS: snprintf(buf, n, "conv_wgrad_rs_kernel<W%d,%s>", d->dy.W, vinet_wgrad_rs_four_wave(d) ? "4w" : "8w"); break;
     case WGRAD_HS: snprintf(buf, n, d->bnb_z ? "conv_wgrad_hs_kernel<bn_bwd>" : "conv_wgrad_hs_kernel"); break;
     case WGRAD_TS: snprintf(buf, n, "conv_wgrad_ts_kernel<%s>", pre); break;
     case WGRAD_TF: snprintf(buf, n, "conv_wgrad_tf_kernel<%s>", pre); break;

@@ -748,6 +748,12 @@ bool vinet_wgrad_use_rs(const VinetWgradDesc* d) {
   return (long)d->dy.B * d->dy.T >= 64 && d->dy.H >= 8;
 }
 
+// the four-wave form (conv_wgrad_rs4_kernel) exists for these row widths; every other width, and wgrad_rs4 = 0, runs the eight-wave kernels
+bool vinet_wgrad_rs_four_wave(const VinetWgradDesc* d) {
+  const int W = d->dy.W;
+  return g_vinet_opt_wgrad_rs4 && (W == 24 || W == 48 || W == 32 || W == 64 || W == 96);
+}
+
 int vinet_launch_wgrad_rs(const VinetWgradDesc* d, hipStream_t s) {
   WgradRsArgs a;
   a.x = (const char*)d->x.ptr; a.dy = (const char*)d->dy.ptr; a.dw = d->dw;
@@ -765,7 +771,7 @@ int vinet_launch_wgrad_rs(const VinetWgradDesc* d, hipStream_t s) {
   if (workers < 1) workers = 1;
   if (workers > a.items) workers = a.items;
   a.workers = workers;
-  if (g_vinet_opt_wgrad_rs4 && (a.W == 24 || a.W == 48 || a.W == 32 || a.W == 64 || a.W == 96)) {
+  if (vinet_wgrad_rs_four_wave(d)) {
     const int ks4 = (a.W == 24 || a.W == 48) ? 3 : a.W / 32;
     const int rows = ks4 * 32 / a.W;
     const int smem4 = (2 * rows + 2) * (a.W + 2) * 128 + 2 * ks4 * 32 * 128;      // RING = 2R + 2 ring rows + two dy tiles
