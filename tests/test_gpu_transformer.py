@@ -31,13 +31,13 @@ def _real_library():
 from tests.gpu_report import note as _note
 
 
-def _to_ncdhw(tokens):
-    """[S, B, E] -> [B, S, 4, 7, 12]"""
-    return tokens.permute(1, 0, 2).reshape(tokens.shape[1], S, 4, 7, 12).contiguous()
+def _to_ncdhw(tokens, thw=(4, 7, 12)):
+    """[S, B, E] -> [B, S, T, H, W] with T H W = E (the model's own 4 x 7 x 12 positions unless told otherwise)"""
+    return tokens.permute(1, 0, 2).reshape(tokens.shape[1], S, *thw).contiguous()
 
 
 def _to_tokens(x):
-    return x.reshape(x.shape[0], S, EF).permute(1, 0, 2)
+    return x.reshape(x.shape[0], S, -1).permute(1, 0, 2)
 
 
 def _encoder(sd, p=None, train=True, seed=1234):
@@ -52,27 +52,27 @@ def _encoder(sd, p=None, train=True, seed=1234):
     return tf.to(DEV).train(train)
 
 
-def _run(tf, x_tokens, proj_tokens, masks=None):
+def _run(tf, x_tokens, proj_tokens, masks=None, thw=(4, 7, 12)):
     """forward + backward of the HIP encoder on tokens [S, B, E]; returns tensors keyed like the block fixture"""
     from vinet_amd import fusion
     for q in tf.parameters():
         q.grad = None
-    x = _to_ncdhw(x_tokens).to(DEV).requires_grad_(True)
+    x = _to_ncdhw(x_tokens, thw).to(DEV).requires_grad_(True)
     y = fusion.transformer_tokens(tf, x, masks)
-    (y * _to_ncdhw(proj_tokens).to(DEV)).sum().backward()
+    (y * _to_ncdhw(proj_tokens, thw).to(DEV)).sum().backward()
     got = {"train_y": _to_tokens(y.detach()), "train_gx": _to_tokens(x.grad)}
     for k, q in tf.named_parameters():
         got["train_g:" + k] = q.grad.clone()
     return got
 
 
-def _torch_run(sd, x, proj, dtype, p=0.0, masks=None):
-    layers = TM.layers_from_state_dict(sd, "transformer_encoder.", NL, dtype)
+def _torch_run(sd, x, proj, dtype, p=0.0, masks=None, nhead=H, n_layers=NL):
+    layers = TM.layers_from_state_dict(sd, "transformer_encoder.", n_layers, dtype)
     for P in layers:
         for t in P.values():
             t.requires_grad_(True)
     xg = x.to(dtype).clone().requires_grad_(True)
-    y = TM.encoder(xg, sd["pos_encoder.pe"].to(dtype), layers, H, p, masks)
+    y = TM.encoder(xg, sd["pos_encoder.pe"].to(dtype), layers, nhead, p, masks)
     (y * proj.to(dtype)).sum().backward()
     got = {"train_y": y.detach(), "train_gx": xg.grad}
     for i, P in enumerate(layers):

@@ -145,3 +145,35 @@ def test_new_parameters_reach_the_optimizer_and_the_gradient_buckets():
     assert len(names) == 4 + 36
     trainable = {id(p) for p in parallel.trainable_parameters(m)}
     assert all(id(p) in trainable for k, p in m.named_parameters() if k in names)
+
+
+@pytest.mark.parametrize("Ef, F, H, NL", [(48, 80, 4, 2), (96, 16, 1, 2)], ids=["e48_f80_h4_l2", "e96_f16_h1_l2"])
+def test_torch_model_equals_nn_transformer_encoder_at_the_small_shapes(Ef, F, H, NL):
+    """tests/transformer_model.py against torch.nn.TransformerEncoder, both fp64, eval mode, at the small shapes
+    tests/test_gpu_transformer_shapes.py leans on: output and every gradient to 1e-12"""
+    from vinet_amd import model as VM
+    torch.manual_seed(5)
+    tf = VM._TransformerParams(Ef, hidden_size=F, nhead=H, num_encoder_layers=NL, max_len=32)
+    sd = synth.synth_state_dict(tf.state_dict(), 13)
+    sd["pos_encoder.pe"] = tf.state_dict()["pos_encoder.pe"]
+    x = synth.normal("tf_small_tokens", (32, 3, Ef), 13).double()
+    proj = synth.normal("tf_small_proj", (32, 3, Ef), 13).double()
+    pe = sd["pos_encoder.pe"].double()
+    layers = TM.layers_from_state_dict(sd, "transformer_encoder.", NL, torch.float64)
+    for P in layers:
+        for t in P.values():
+            t.requires_grad_(True)
+    xa = x.clone().requires_grad_(True)
+    ya = TM.encoder(xa, pe, layers, H)
+    (ya * proj).sum().backward()
+    enc = torch.nn.TransformerEncoder(torch.nn.TransformerEncoderLayer(Ef, H, F), NL, enable_nested_tensor=False).double().eval()
+    enc.load_state_dict({k[len("transformer_encoder."):]: v.double() for k, v in sd.items() if k.startswith("transformer_encoder.")})
+    xb = x.clone().requires_grad_(True)
+    yb = enc(xb + pe)
+    (yb * proj).sum().backward()
+    assert float((ya - yb).detach().abs().max()) <= 1e-12
+    assert float((xa.grad - xb.grad).abs().max()) <= 1e-12
+    theirs = dict(enc.named_parameters())
+    for i, P in enumerate(layers):
+        for k, t in P.items():
+            assert float((t.grad - theirs["layers.%d.%s" % (i, k)].grad).abs().max()) <= 1e-12, (i, k)

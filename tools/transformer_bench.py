@@ -7,7 +7,7 @@
 
 Warm-up, then the median of --repeats timed runs (device events around one call).  One JSON line per measurement on stdout.
 
-    python tools/transformer_bench.py [--what encoder,step] [--repeats 30] [--step_batches 1,8,32,192] [--dtype bf16]
+    python tools/transformer_bench.py [--what encoder,step] [--repeats 30] [--encoder_batches 1,8,32,192] [--step_batches 1,8,32,192] [--dtype bf16]
 """
 import argparse
 import json
@@ -52,7 +52,7 @@ def bench_encoder(args, dev):
     aten = torch.nn.TransformerEncoder(torch.nn.TransformerEncoderLayer(336, 4, 336, dropout=0.0), 3).to(dev).train()
     aten.load_state_dict({k[len("transformer_encoder."):]: v for k, v in sd.items() if k.startswith("transformer_encoder.")})
     pe = sd["pos_encoder.pe"].to(dev)
-    for B in (1, 8, 32, 192):
+    for B in [int(b) for b in args.encoder_batches.split(",")]:
         x = synth.normal("bench_x", (B, 32, 4, 7, 12), 2).to(dev)
         g = synth.normal("bench_g", (B, 32, 4, 7, 12), 3).to(dev)
         xt = x.reshape(B, 32, 336).permute(1, 0, 2).contiguous()
@@ -136,6 +136,7 @@ def main():
     p.add_argument("--repeats", default=30, type=int)
     p.add_argument("--step_repeats", default=9, type=int)
     p.add_argument("--step_batches", default="1,8,32,192")
+    p.add_argument("--encoder_batches", default="1,8,32,192")
     p.add_argument("--dtype", default="bf16")
     args = p.parse_args()
     dev = torch.device("cuda:0")

@@ -11,7 +11,7 @@
 // All GEMMs run on v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation, in every context (a bf16 context differs in
 // the two boundary kernels only).  Softmax rows and LayerNorm statistics are fp32 and SAVED by forward (16 KB + 512 B per clip
 // and layer); dropout keep masks are RECOMPUTED by backward from (seed, step, layer, site, element).
-// Determinism: a weight gradient is one workgroup's sequential sum over all tokens (from 1024 tokens on: over 512-token slices,
+// Determinism: a weight gradient is one workgroup's sequential sum over all tokens (above 512 tokens: over 512-token slices,
 // whose partial matrices are added in slice order); the small gradients are per-clip partial sums reduced over clips in index
 // order.  No atomics anywhere.
 #include "common.h"
@@ -465,7 +465,9 @@ static Layout make_layout(const VinetTransformerDesc* d) {
     L.pstride = 9 * L.E + L.F;
     L.part = o; o += (long)d->B * L.pstride;
     // weight gradients of many clips: the token axis is cut into TF_WGRAD_CHUNK-token slices, one partial matrix each
-    L.nsplit = L.M >= 2 * TF_WGRAD_CHUNK ? (L.M + TF_WGRAD_CHUNK - 1) / TF_WGRAD_CHUNK : 1;
+    // (no sequential sum runs over more than one slice: at 992 tokens in one launch linear1's weight gradient was 4.07 x the torch
+    //  model's own fp32 error from the fp64 result, tests/test_gpu_transformer_shapes.py)
+    L.nsplit = L.M > TF_WGRAD_CHUNK ? (L.M + TF_WGRAD_CHUNK - 1) / TF_WGRAD_CHUNK : 1;
     L.wsplit = o;
     if (L.nsplit > 1) o += L.nsplit * 3 * L.E * (L.F > L.E ? L.F : L.E);
   }
@@ -509,7 +511,7 @@ static void gemm(hipStream_t s, const float* A, int lda, const float* Bm, int ld
   }
 }
 
-// dW[rows][cols] += dY^T X over all M tokens.  Few clips: one launch, every workgroup sums all tokens in order.  Many clips: slices
+// dW[rows][cols] += dY^T X over all M tokens.  Up to 16 clips: one launch, every workgroup sums all tokens in order.  Many clips: slices
 // of TF_WGRAD_CHUNK tokens into partial matrices, then one pass adds them in slice order -- fixed for a given batch either way.
 static void wgrad(hipStream_t s, const Layout& L, float* ws, const float* dY, int ldy, const float* X, int ldx, float* dW, int rows, int cols, int M) {
   GemmEpi ep;
