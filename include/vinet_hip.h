@@ -360,6 +360,12 @@ int vinet_maxpool3d(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pr
                     uint8_t* argmax, void* stream);
 int vinet_maxpool3d_bwd(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax, const VinetTensor* dx,
                         int32_t accumulate, void* stream);
+/* Name of the kernel the call with these very arguments will launch, with its dtype: "maxpool_fwd8_kernel<bf16>",
+ * "maxpool_k3s1_pk_kernel" (pure host code: the pointers are tested for null and alignment only). */
+int vinet_maxpool3d_kernel_name(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
+                                const uint8_t* argmax, char* buf, int32_t n);
+int vinet_maxpool3d_bwd_kernel_name(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax,
+                                    const VinetTensor* dx, char* buf, int32_t n);
 
 /* nn.Upsample(scale_factor=(1,2,2), mode='trilinear', align_corners=False)
  * (model.py:254,258,263,268,273,278) and its backward. */
@@ -632,8 +638,9 @@ int vinet_gt_preprocess(const uint8_t* src, int32_t N, int32_t H, int32_t W, flo
  *   "pack_tiled" (1): LDS-tiled multi-tensor pack / unpack; 0 = the element-wise kernels
  *   "pool_lds" (1): LDS halo-tile 3x3x3/s1 max-pool forward (C % 64 == 0): 0 off, 1 large tensors, 2 always
  *   "pool_pk" (1): bf16: packed 32-bit-key form of the LDS halo-tile pool; 0 = the fp32-compare kernel
- *   "pool_twalk" (1): T-walking 3x3x3/s1 max-pool backward: 0 off, 1 large tensors, 2 always, 3 conditional-load form, 4
- *       bf16 without the EXEC-mask routing
+ *   "pool_twalk" (1): T-walking 3x3x3/s1 max-pool backward: 0 off, 1 large tensors, 2 always (any value above 3 too), 3
+ *       conditional-load form.  The forward's 8-channel T-walking kernel (kT 3, sT 1) reads it too: >= 2 forces it on
+ *       small tensors, 0 does NOT switch it off
  *   "pool_blk" (1): strided max-pool backward per 2x2 input block; 0 off
  *   "up_blk" (1): 8-channel upsample kernels (forward per 2x2 output block); 0 off
  *   "auc_ws" (0): AUC-Judd sorts and counts in the caller's workspace whatever the number of fixations: 1 on (tests)

@@ -86,6 +86,28 @@ def wgrad_name(lib, d):
     return buf.value.decode()
 
 
+def pool_args(ksp, dt, dims, chan, pre="affine_relu", am="ok"):
+    """(descriptor, x, pre, y, argmax) as tests.test_gpu_kernels.test_maxpool builds them, without tensors: x (and dx) a channel slice
+    (C, ld, c_off) of a wider buffer, y (and dy) dense unless a fourth element of `chan` gives its ld"""
+    k, s, p = ksp
+    B, T, H, W = dims
+    Cc, ld, c_off, y_ld = (tuple(chan) + (None,))[:4]
+    oT, oH, oW = [(d + 2 * pp - kk) // ss + 1 for d, kk, ss, pp in zip((T, H, W), k, s, p)]
+    x = _ct(B, T, H, W, Cc, ld, None, E.ESIZE[dt], c_off)
+    y = _ct(B, oT, oH, oW, Cc, y_ld, None, E.ESIZE[dt])
+    aff = {"none": L.CAffine(None, None, 0), "relu": L.CAffine(None, None, 1), "affine_relu": L.CAffine(_P, _P, 1), "scale_only": L.CAffine(_P, None, 1)}[pre]
+    return L.CPoolDesc(dt, *(k + s + p)), x, aff, y, {"ok": _P, "null": None, "+4": _P + 4}[am]
+
+
+def pool_names(lib, d, x, pre, y, argmax):
+    """(forward, backward) kernel of vinet_maxpool3d(d, x, pre, y, argmax) and vinet_maxpool3d_bwd(d, dy = y's view, argmax, dx = x's view);
+    None where the library rejects the arguments (the backward without an argmax)"""
+    buf = C.create_string_buffer(128)
+    fwd = buf.value.decode() if lib.vinet_maxpool3d_kernel_name(C.byref(d), C.byref(x), pre, C.byref(y), argmax, buf, 128) == 0 else None
+    bwd = buf.value.decode() if lib.vinet_maxpool3d_bwd_kernel_name(C.byref(d), C.byref(y), argmax, C.byref(x), buf, 128) == 0 else None
+    return fwd, bwd
+
+
 def option_defaults(path):
     """{name: default} out of options.h (the defaults are integer expressions: `28 * 48`)"""
     out = {}
@@ -191,3 +213,78 @@ WGRAD_NAMES_RUN = (["conv_wgrad_rs_kernel<W%d,4w>" % w for w in (24, 48, 32, 64,
                    ["conv_wgrad_dma_kernel<64,64,%d,%s>" % (tg, f) for tg in (1, 2, 3, 7, 9) for f in ("plain", "pre")])
 WGRAD_NAMES_NOT_RUN = {"conv_wgrad_dma_kernel<128,128,1,plain>": "wgrad_dma.hip:387, unreachable: wg_pick never answers a 128-row tile",
                        "conv_wgrad_dma_kernel<128,128,1,pre>": "wgrad_dma.hip:387, unreachable for the same reason"}
+
+
+# ---- max-pool routes (pool.hip: pool_fwd_route / pool_bwd_route) ----
+# (key, pool, dtype, (B, T, H, W), (C, ld, c_off[, ld of y]), pre, argmax, options) -> forward kernel, backward kernel (None: rejected, the
+# backward needs an argmax).  The names were recorded from the if-chains the two entry points had before the routes existed (each branch
+# made to answer its kernel's name); the routes must reproduce every row.  Shapes too big to launch are here by descriptor alone.
+F32, BF16 = E.F32, E.BF16
+P0, P1, K3 = ((1, 3, 3), (1, 2, 2), (0, 1, 1)), ((3, 3, 3), (2, 2, 2), (1, 1, 1)), ((3, 3, 3), (1, 1, 1), (1, 1, 1))
+P3, T3 = ((2, 1, 1), (2, 1, 1), (0, 0, 0)), ((3, 1, 1), (1, 1, 1), (1, 0, 0))
+SM, OCT, QUAD = (2, 8, 9, 10), (24, 40, 8), (12, 28, 8)      # the kernel suite's small clip; 8- and 4-channel slices of a wider buffer
+C65536, C65535, ONE = (1, 2, 256, 256), (1, 2, 255, 257), (8, 8, 0)      # one channel octet: H x W 8-channel columns
+POOL_TABLE = [
+    ('natural_k133s2_f32', P0, F32, SM, OCT, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_kernel<f32>', 'maxpool_bwd_k133s2_kernel<f32>'),
+    ('natural_k333s2_f32', P1, F32, SM, OCT, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_kernel<f32>', 'maxpool_bwd_k3s2_kernel<f32>'),
+    ('natural_k333s1_f32', K3, F32, SM, OCT, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_kernel<f32>', 'maxpool_bwd_k3s1_kernel<f32>'),
+    ('natural_k211s2_f32', P3, F32, SM, OCT, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_kernel<f32>', 'maxpool_bwd8_kernel<f32>'),
+    ('c12_k133s2_f32', P0, F32, SM, QUAD, 'affine_relu', 'ok', dict(), 'maxpool_fwd_kernel<f32>', 'maxpool_bwd_kernel<f32>'),
+    ('c12_k333s1_f32', K3, F32, SM, QUAD, 'affine_relu', 'ok', dict(), 'maxpool_tslide_kernel<f32>', 'maxpool_bwd_kernel<f32>'),
+    ('lds2_f32', K3, F32, SM, OCT, 'affine_relu', 'ok', dict(pool_lds=2), 'maxpool_k3s1_lds_kernel<f32>', 'maxpool_bwd_k3s1_kernel<f32>'),
+    ('twalk2_f32', K3, F32, SM, OCT, 'affine_relu', 'ok', dict(pool_twalk=2), 'maxpool_tslide8_kernel<f32>', 'maxpool_bwd_k3s1_twalk_kernel<f32>'),
+    ('twalk2_lds0_f32', K3, F32, SM, OCT, 'affine_relu', 'ok', dict(pool_twalk=2, pool_lds=0), 'maxpool_tslide8_kernel<f32>', 'maxpool_bwd_k3s1_twalk_kernel<f32>'),
+    ('twalk3_f32', K3, F32, SM, OCT, 'affine_relu', 'ok', dict(pool_twalk=3, pool_lds=0), 'maxpool_tslide8_kernel<f32>', 'maxpool_bwd_k3s1_twalk_kernel<f32>'),
+    ('blk0_k133s2_f32', P0, F32, SM, OCT, 'affine_relu', 'ok', dict(pool_blk=0), 'maxpool_fwd8_kernel<f32>', 'maxpool_bwd8_kernel<f32>'),
+    ('blk0_k333s2_f32', P1, F32, SM, OCT, 'affine_relu', 'ok', dict(pool_blk=0), 'maxpool_fwd8_kernel<f32>', 'maxpool_bwd8_kernel<f32>'),
+    ('cols65536_f32', K3, F32, C65536, ONE, 'affine_relu', 'ok', dict(), 'maxpool_k3s1_lds_kernel<f32>', 'maxpool_bwd_k3s1_twalk_kernel<f32>'),
+    ('cols65535_f32', K3, F32, C65535, ONE, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_kernel<f32>', 'maxpool_bwd_k3s1_kernel<f32>'),
+    ('cols65536_lds0_f32', K3, F32, C65536, ONE, 'affine_relu', 'ok', dict(pool_lds=0), 'maxpool_tslide8_kernel<f32>', 'maxpool_bwd_k3s1_twalk_kernel<f32>'),
+    ('cols65535_lds0_f32', K3, F32, C65535, ONE, 'affine_relu', 'ok', dict(pool_lds=0), 'maxpool_fwd8_kernel<f32>', 'maxpool_bwd_k3s1_kernel<f32>'),
+    ('cols65536_k311_f32', T3, F32, C65536, ONE, 'affine_relu', 'ok', dict(), 'maxpool_tslide8_kernel<f32>', 'maxpool_bwd8_kernel<f32>'),
+    ('cols65535_k311_f32', T3, F32, C65535, ONE, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_kernel<f32>', 'maxpool_bwd8_kernel<f32>'),
+    ('natural_k133s2_bf16', P0, BF16, SM, OCT, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k133s2_kernel<bf16>'),
+    ('natural_k333s2_bf16', P1, BF16, SM, OCT, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k3s2_kernel<bf16>'),
+    ('natural_k333s1_bf16', K3, BF16, SM, OCT, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('natural_k211s2_bf16', P3, BF16, SM, OCT, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd8_kernel<bf16>'),
+    ('c12_k133s2_bf16', P0, BF16, SM, QUAD, 'affine_relu', 'ok', dict(), 'maxpool_fwd_kernel<bf16>', 'maxpool_bwd_kernel<bf16>'),
+    ('c12_k333s1_bf16', K3, BF16, SM, QUAD, 'affine_relu', 'ok', dict(), 'maxpool_tslide_kernel<bf16>', 'maxpool_bwd_kernel<bf16>'),
+    ('lds2_bf16', K3, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_lds=2), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('twalk2_bf16', K3, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_twalk=2), 'maxpool_tslide8_kernel<bf16>', 'maxpool_bwd_k3s1_tw3_kernel'),
+    ('twalk2_lds0_bf16', K3, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_twalk=2, pool_lds=0), 'maxpool_tslide8_kernel<bf16>', 'maxpool_bwd_k3s1_tw3_kernel'),
+    ('twalk3_bf16', K3, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_twalk=3, pool_lds=0), 'maxpool_tslide8_kernel<bf16>', 'maxpool_bwd_k3s1_twalk_kernel<bf16>'),
+    ('blk0_k133s2_bf16', P0, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_blk=0), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd8_kernel<bf16>'),
+    ('blk0_k333s2_bf16', P1, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_blk=0), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd8_kernel<bf16>'),
+    ('cols65536_bf16', K3, BF16, C65536, ONE, 'affine_relu', 'ok', dict(), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_tw3_kernel'),
+    ('cols65535_bf16', K3, BF16, C65535, ONE, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('cols65536_lds0_bf16', K3, BF16, C65536, ONE, 'affine_relu', 'ok', dict(pool_lds=0), 'maxpool_tslide8_kernel<bf16>', 'maxpool_bwd_k3s1_tw3_kernel'),
+    ('cols65535_lds0_bf16', K3, BF16, C65535, ONE, 'affine_relu', 'ok', dict(pool_lds=0), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('cols65536_k311_bf16', T3, BF16, C65536, ONE, 'affine_relu', 'ok', dict(), 'maxpool_tslide8_kernel<bf16>', 'maxpool_bwd8_kernel<bf16>'),
+    ('cols65535_k311_bf16', T3, BF16, C65535, ONE, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd8_kernel<bf16>'),
+    ('pk0_lds2', K3, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_pk=0, pool_lds=2), 'maxpool_k3s1_lds_kernel<bf16>', 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('pk0_k133s2', P0, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_pk=0), 'maxpool_fwd8_kernel<bf16>', 'maxpool_bwd_k133s2_kernel<bf16>'),
+    ('scale_only_lds2', K3, BF16, SM, OCT, 'scale_only', 'ok', dict(pool_lds=2), 'maxpool_k3s1_lds_kernel<bf16>', 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('scale_only_k133s2', P0, BF16, SM, OCT, 'scale_only', 'ok', dict(), 'maxpool_fwd8_kernel<bf16>', 'maxpool_bwd_k133s2_kernel<bf16>'),
+    ('no_pre_lds2', K3, BF16, SM, OCT, 'none', 'ok', dict(pool_lds=2), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('relu_only_k133s2', P0, BF16, SM, OCT, 'relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k133s2_kernel<bf16>'),
+    ('t1_lds2', K3, BF16, (2, 1, 9, 10), OCT, 'affine_relu', 'ok', dict(pool_lds=2, pool_twalk=2), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k3s1_tw3_kernel'),
+    ('t2_lds2', K3, BF16, (2, 2, 9, 10), OCT, 'affine_relu', 'ok', dict(pool_lds=2, pool_twalk=2), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_tw3_kernel'),
+    ('t1_c12', K3, BF16, (2, 1, 9, 10), QUAD, 'affine_relu', 'ok', dict(), 'maxpool_fwd_kernel<bf16>', 'maxpool_bwd_kernel<bf16>'),
+    ('t2_c12', K3, BF16, (2, 2, 9, 10), QUAD, 'affine_relu', 'ok', dict(), 'maxpool_tslide_kernel<bf16>', 'maxpool_bwd_kernel<bf16>'),
+    ('t1_cols65536', K3, BF16, (1, 1, 256, 256), ONE, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k3s1_tw3_kernel'),
+    ('argmax_plus4_k333s1', K3, BF16, SM, OCT, 'affine_relu', '+4', dict(), 'maxpool_fwd_kernel<bf16>', 'maxpool_bwd_kernel<bf16>'),
+    ('argmax_plus4_lds2_twalk2', K3, BF16, SM, OCT, 'affine_relu', '+4', dict(pool_lds=2, pool_twalk=2), 'maxpool_fwd_kernel<bf16>', 'maxpool_bwd_kernel<bf16>'),
+    ('argmax_plus4_k133s2', P0, BF16, SM, OCT, 'affine_relu', '+4', dict(), 'maxpool_fwd_kernel<bf16>', 'maxpool_bwd_kernel<bf16>'),
+    ('argmax_plus4_c12', K3, F32, SM, QUAD, 'affine_relu', '+4', dict(), 'maxpool_tslide_kernel<f32>', 'maxpool_bwd_kernel<f32>'),
+    ('argmax_null_k333s1', K3, BF16, SM, OCT, 'affine_relu', 'null', dict(), 'maxpool_fwd8_pk_kernel', None),
+    ('argmax_null_cols65536', K3, BF16, C65536, ONE, 'affine_relu', 'null', dict(), 'maxpool_k3s1_pk_kernel', None),
+    ('argmax_null_c12', P0, F32, SM, QUAD, 'affine_relu', 'null', dict(), 'maxpool_fwd_kernel<f32>', None),
+    ('twalk0_cols65536', K3, BF16, C65536, ONE, 'affine_relu', 'ok', dict(pool_twalk=0), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('twalk0_lds0_cols65536', K3, BF16, C65536, ONE, 'affine_relu', 'ok', dict(pool_twalk=0, pool_lds=0), 'maxpool_tslide8_kernel<bf16>', 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('twalk3_cols65536', K3, BF16, C65536, ONE, 'affine_relu', 'ok', dict(pool_twalk=3), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_twalk_kernel<bf16>'),
+    ('lds0_pk0_cols65536', K3, BF16, C65536, ONE, 'affine_relu', 'ok', dict(pool_lds=0, pool_pk=0), 'maxpool_tslide8_kernel<bf16>', 'maxpool_bwd_k3s1_tw3_kernel'),
+    ('plane_2p30', K3, BF16, (1, 2, 4096, 4096), (64, 64, 0), 'affine_relu', 'ok', dict(), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_twalk_kernel<bf16>'),
+    ('plane_2p30_f32', K3, F32, (1, 2, 4096, 4096), (64, 64, 0), 'affine_relu', 'ok', dict(), 'maxpool_k3s1_lds_kernel<f32>', 'maxpool_bwd_k3s1_twalk_kernel<f32>'),
+    ('plane_2p27', K3, BF16, (1, 2, 4096, 4096), ONE, 'affine_relu', 'ok', dict(), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_tw3_kernel'),
+    ('plane_2p30_dy_ld', K3, BF16, (1, 2, 4096, 4096), (8, 8, 0, 64), 'affine_relu', 'ok', dict(), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_twalk_kernel<bf16>'),
+]

@@ -1505,16 +1505,21 @@ POOLS = [((1, 3, 3), (1, 2, 2), (0, 1, 1)), ((3, 3, 3), (2, 2, 2), (1, 1, 1)), (
          ((8, 1, 1), (8, 1, 1), (0, 0, 0))]
 
 
-@pytest.mark.parametrize("form", [2, 3, 4])
+def _tn(dt):
+    return "f32" if dt == E.F32 else "bf16"
+
+
+@pytest.mark.parametrize("form", [2, 3])
 @pytest.mark.parametrize("dt", DTS)
 def test_maxpool_k3s1_twalk_backward(dt, form):
     """the T-walking 3x3x3/s1 backward (chosen for large tensors only) forced on the small test shape
-    (2: bf16 takes the all-loads-up-front form with EXEC-mask routing; 3: the conditional-load form for every dtype;
-    4: bf16 all-loads-up-front with compare / select / add routing)"""
+    (2: bf16 takes the all-loads-up-front form with EXEC-mask routing; 3: the conditional-load form for every dtype).
+    The option forces the forward's 8-channel T-walk as well."""
     lib = _lib()
     assert lib.vinet_set_option(b"pool_twalk", form) == 0 and lib.vinet_set_option(b"pool_lds", 0) == 0
     try:
-        test_maxpool(dt, ((3, 3, 3), (1, 1, 1), (1, 1, 1)))
+        _maxpool(dt, ((3, 3, 3), (1, 1, 1), (1, 1, 1)), expect_fwd="maxpool_tslide8_kernel<%s>" % _tn(dt),
+                 expect_bwd="maxpool_bwd_k3s1_tw3_kernel" if (form, dt) == (2, E.BF16) else "maxpool_bwd_k3s1_twalk_kernel<%s>" % _tn(dt))
     finally:
         lib.vinet_set_option(b"pool_twalk", 1)
         lib.vinet_set_option(b"pool_lds", 1)
@@ -1525,7 +1530,7 @@ def test_maxpool_k3s1_twalk_backward(dt, form):
 @pytest.mark.parametrize("Cc,hw", [(136, (17, 8)), (64, (8, 24))])
 def test_maxpool_k3s2_block_backward_shapes(Cc, hw, acc, dt):
     """the 2x2x2-block 3x3x3/s2 backward on more shapes: odd and even extents, several channel octets, store and accumulate"""
-    test_maxpool(dt, POOLS[1], Cc=Cc, acc=acc, hw=hw)
+    _maxpool(dt, POOLS[1], Cc=Cc, acc=acc, hw=hw, expect_bwd="maxpool_bwd_k3s2_kernel<%s>" % _tn(dt))
 
 
 @pytest.mark.parametrize("acc", [0, 1])
@@ -1535,7 +1540,7 @@ def test_maxpool_k3s1_backward_shapes(Cc, hw, acc):
     lib = _lib()
     assert lib.vinet_set_option(b"pool_twalk", 2) == 0
     try:
-        test_maxpool(E.BF16, ((3, 3, 3), (1, 1, 1), (1, 1, 1)), Cc=Cc, acc=acc, hw=hw)
+        _maxpool(E.BF16, ((3, 3, 3), (1, 1, 1), (1, 1, 1)), Cc=Cc, acc=acc, hw=hw, expect_bwd="maxpool_bwd_k3s1_tw3_kernel")
     finally:
         lib.vinet_set_option(b"pool_twalk", 1)
 
@@ -1546,8 +1551,8 @@ def test_maxpool_133s2_generic_backward(dt):
     lib = _lib()
     assert lib.vinet_set_option(b"pool_blk", 0) == 0
     try:
-        test_maxpool(dt, POOLS[0])
-        test_maxpool(dt, POOLS[1])
+        _maxpool(dt, POOLS[0], expect_bwd="maxpool_bwd8_kernel<%s>" % _tn(dt))
+        _maxpool(dt, POOLS[1], expect_bwd="maxpool_bwd8_kernel<%s>" % _tn(dt))
     finally:
         lib.vinet_set_option(b"pool_blk", 1)
 
@@ -1557,9 +1562,9 @@ def test_maxpool_k3s1_lds_forward_bf16_fp32_compare():
     lib = _lib()
     assert lib.vinet_set_option(b"pool_pk", 0) == 0
     try:
-        test_maxpool_k3s1_lds_forward(E.BF16)
+        _maxpool_lds(E.BF16, "maxpool_k3s1_lds_kernel<bf16>")
         for ksp in POOLS[:3]:                      # the generic 8-channel kernel, fp32 compare
-            test_maxpool(E.BF16, ksp)
+            _maxpool(E.BF16, ksp, expect_fwd="maxpool_fwd8_kernel<bf16>")
     finally:
         lib.vinet_set_option(b"pool_pk", 1)
 
@@ -1567,11 +1572,15 @@ def test_maxpool_k3s1_lds_forward_bf16_fp32_compare():
 @pytest.mark.parametrize("dt", DTS)
 def test_maxpool_k3s1_lds_forward(dt):
     """the LDS halo-tile 3x3x3/s1 forward (chosen for large tensors only) forced on the small test shape
-    (partial spatial tiles, partial channel group)"""
+    (partial spatial tiles, partial channel group): fp32 compares, bf16 on packed keys"""
+    _maxpool_lds(dt, "maxpool_k3s1_lds_kernel<f32>" if dt == E.F32 else "maxpool_k3s1_pk_kernel")
+
+
+def _maxpool_lds(dt, expect_fwd):
     lib = _lib()
     assert lib.vinet_set_option(b"pool_lds", 2) == 0
     try:
-        test_maxpool(dt, ((3, 3, 3), (1, 1, 1), (1, 1, 1)))
+        _maxpool(dt, ((3, 3, 3), (1, 1, 1), (1, 1, 1)), expect_fwd=expect_fwd)
     finally:
         lib.vinet_set_option(b"pool_lds", 1)
 
@@ -1582,12 +1591,29 @@ def test_maxpool_k3s1_lds_forward(dt):
 def test_maxpool_strided_odd_extents(ksp, Cc, hw, T):
     """the strided 3 x 3 spatial pools (forward, and the 2x2 / 2x2x2-block backward kernels) on odd / unit clip lengths, odd and
     even H / W, several channel octets"""
-    test_maxpool(E.BF16, ksp, Cc=Cc, hw=hw, T=T)
+    _maxpool(E.BF16, ksp, Cc=Cc, hw=hw, T=T, expect_fwd="maxpool_fwd8_pk_kernel",
+             expect_bwd="maxpool_bwd_k133s2_kernel<bf16>" if ksp == POOLS[0] else "maxpool_bwd_k3s2_kernel<bf16>")
 
 
+def _pool_kernel(query, *args):
+    buf = C.create_string_buffer(128)
+    assert getattr(_lib(), query)(*args, buf, 128) == 0, _lib().vinet_last_error()
+    return buf.value.decode()
+
+
+# every pool at 24 channels; then 12 channels (C % 8 != 0) on a wider buffer: the 4-channel kernels, which no 8-channel-aligned case
+# reaches, store and accumulate
 @pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("ksp", POOLS, ids=[str(p[0]) + str(p[1]) for p in POOLS])
-def test_maxpool(dt, ksp, Cc=24, acc=1, hw=(9, 10), T=8):
+@pytest.mark.parametrize("ksp,Cc,acc,expect_fwd,expect_bwd", [pytest.param(p, 24, 1, None, None, id=str(p[0]) + str(p[1])) for p in POOLS] + [
+    pytest.param(POOLS[i], 12, acc, "maxpool_%s_kernel<T>" % fwd, "maxpool_bwd_kernel<T>", id=str(POOLS[i][0]) + str(POOLS[i][1]) + "-c12-acc%d" % acc)
+    for i, fwd in ((0, "fwd"), (2, "tslide")) for acc in (0, 1)])
+def test_maxpool(dt, ksp, Cc, acc, expect_fwd, expect_bwd):
+    _maxpool(dt, ksp, Cc=Cc, acc=acc, expect_fwd=expect_fwd, expect_bwd=expect_bwd)
+
+
+def _maxpool(dt, ksp, Cc=24, acc=1, hw=(9, 10), T=8, expect_fwd=None, expect_bwd=None):
+    """expect_fwd / expect_bwd: the kernels this case is meant to run ("<T>": the dtype's instantiation), asked of the library with the very
+    arguments of the two launches"""
     k, s, p = ksp
     B, (H, W) = 2, hw
     od = [(d + 2 * pp - kk) // ss + 1 for d, kk, ss, pp in zip((T, H, W), k, s, p)]
@@ -1598,7 +1624,10 @@ def test_maxpool(dt, ksp, Cc=24, acc=1, hw=(9, 10), T=8):
 
     def pd():
         return L.CPoolDesc(dt, k[0], k[1], k[2], s[0], s[1], s[2], p[0], p[1], p[2])
-    run_both("vinet_maxpool3d", lambda sd: [C.byref(pd()), C.byref(xmk(sd).ct()), L.CAffine(ps.ptr(sd), ph.ptr(sd), 1), C.byref(ymk(sd).ct()), am.ptr(sd), _stream() if sd == "gpu" else 0])
+    fwd_args = lambda sd: [C.byref(pd()), C.byref(xmk(sd).ct()), L.CAffine(ps.ptr(sd), ph.ptr(sd), 1), C.byref(ymk(sd).ct()), am.ptr(sd)]
+    if expect_fwd:
+        assert _pool_kernel("vinet_maxpool3d_kernel_name", *fwd_args("gpu")) == expect_fwd.replace("<T>", "<%s>" % _tn(dt))
+    run_both("vinet_maxpool3d", lambda sd: fwd_args(sd) + [_stream() if sd == "gpu" else 0])
     _cmp(yp.get("gpu"), yp.get("cpu"), 1e-6 if dt == E.F32 else 1e-2, "maxpool")
     # ReLU creates ties at 0: indices may only differ where the pooled value is 0
     diff = am.get("gpu") != am.get("cpu")
@@ -1606,7 +1635,10 @@ def test_maxpool(dt, ksp, Cc=24, acc=1, hw=(9, 10), T=8):
     gp, gmk = view_pair(B, od[0], od[1], od[2], Cc, dt, "pg", 5)
     dxp, dxmk = view_pair(B, T, H, W, Cc, dt, "pdx", 6, ld=Cc + 16, c_off=8)
     amc = Pair(am.cpu.clone())
-    run_both("vinet_maxpool3d_bwd", lambda sd: [C.byref(pd()), C.byref(gmk(sd).ct()), amc.ptr(sd), C.byref(dxmk(sd).ct()), acc, _stream() if sd == "gpu" else 0])
+    bwd_args = lambda sd: [C.byref(pd()), C.byref(gmk(sd).ct()), amc.ptr(sd), C.byref(dxmk(sd).ct())]
+    if expect_bwd:
+        assert _pool_kernel("vinet_maxpool3d_bwd_kernel_name", *bwd_args("gpu")) == expect_bwd.replace("<T>", "<%s>" % _tn(dt))
+    run_both("vinet_maxpool3d_bwd", lambda sd: bwd_args(sd) + [acc, _stream() if sd == "gpu" else 0])
     _cmp(dxp.get("gpu"), dxp.get("cpu"), 1e-5 if dt == E.F32 else 2e-2, "maxpool bwd")
 
 

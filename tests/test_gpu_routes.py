@@ -438,10 +438,10 @@ OPTION_ROWS = {
     "reduce_il": dict(kind="custom", test="test_option_bn_reductions", values=[0]),
     "reduce_small": dict(kind="custom", test="test_option_bn_reductions", values=[0]),
     "pack_tiled": _exempt("swept", "test_pack_weights_multi_matches_single_packs"),
-    "pool_lds": _exempt("swept", "test_maxpool_k3s1_lds_forward"),
-    "pool_pk": _exempt("swept", "test_maxpool_k3s1_lds_forward_bf16_fp32_compare"),
-    "pool_twalk": _exempt("swept", "test_maxpool_k3s1_twalk_backward"),
-    "pool_blk": _exempt("swept", "test_maxpool_133s2_generic_backward"),
+    "pool_lds": _exempt("swept, the kernel asserted by name; every value's route: tests/route_cases.py POOL_TABLE", "test_maxpool_k3s1_lds_forward"),
+    "pool_pk": _exempt("swept, the kernel asserted by name; every value's route: tests/route_cases.py POOL_TABLE", "test_maxpool_k3s1_lds_forward_bf16_fp32_compare"),
+    "pool_twalk": _exempt("swept, the kernel asserted by name; every value's route: tests/route_cases.py POOL_TABLE", "test_maxpool_k3s1_twalk_backward"),
+    "pool_blk": _exempt("swept, the kernel asserted by name; every value's route: tests/route_cases.py POOL_TABLE", "test_maxpool_133s2_generic_backward"),
     "up_blk": _exempt("swept", "test_upsample_quad_kernels"),
     "auc_ws": _exempt("swept", "test_lds_route_and_workspace_route_agree_bit_for_bit"),
     "sauc_ws": _exempt("swept", "test_lds_route_and_workspace_route_agree_bit_for_bit"),

@@ -154,3 +154,22 @@ def test_tperm_weight_gradient_cases_take_the_permuted_order():
         assert d.dy.T > 1 and (d.dy.H * d.dy.W) % (64 if "_pp_" in name else 32) == 0, c[0][0]
         seen.add(name.split("<")[0] + ("<%d>" % c[3]["wgrad_pp"] if "_pp_" in name else ""))
     assert seen == {"conv_wgrad_pp_kernel<3>", "conv_wgrad_pp_kernel<4>", "conv_wgrad_dma_kernel"}, seen
+
+
+def test_pool_table_names_every_instantiation_of_pool_hip():
+    src = _src("pool.hip")
+    typed, plain = re.findall(r"hipLaunchKernelGGL\((\w+)<T>", src), re.findall(r"hipLaunchKernelGGL\((\w+),", src)
+    assert len(typed) == len(set(typed)) == 11 and len(plain) == len(set(plain)) == 3      # DISPATCH_T: two dtypes per typed site
+    inst = {"%s<%s>" % (k, t) for k in typed for t in ("f32", "bf16")} | set(plain)
+    assert len(inst) == 25 and len([n for n in inst if "_bwd" in n]) == 13
+    assert {c[8] for c in R.POOL_TABLE} | {c[9] for c in R.POOL_TABLE} - {None} == inst
+    assert len({c[0] for c in R.POOL_TABLE}) == len(R.POOL_TABLE)
+    for opt, values in (("pool_lds", {0, 1, 2}), ("pool_pk", {0, 1}), ("pool_twalk", {0, 1, 2, 3}), ("pool_blk", {0, 1})):      # every documented value
+        assert {c[7].get(opt, G.OPT_DEFAULTS[opt]) for c in R.POOL_TABLE} == values, opt
+
+
+def test_pool_table_routes_on_the_host():
+    lib = L.load()
+    for key, ksp, dt, dims, chan, pre, am, opts, fwd, bwd in R.POOL_TABLE:
+        with R.options(lib, opts, G.OPT_DEFAULTS):
+            assert R.pool_names(lib, *R.pool_args(ksp, dt, dims, chan, pre, am)) == (fwd, bwd), key

@@ -49,7 +49,7 @@
   VN_OPT(pack_tiled,   1, "LDS-tiled multi-tensor pack / unpack; 0 = the element-wise kernels") \
   VN_OPT(pool_lds,     1, "LDS halo-tile 3x3x3/s1 max-pool forward (C % 64 == 0): 0 off, 1 large tensors, 2 always") \
   VN_OPT(pool_pk,      1, "bf16: packed 32-bit-key form of the LDS halo-tile pool; 0 = the fp32-compare kernel") \
-  VN_OPT(pool_twalk,   1, "T-walking 3x3x3/s1 max-pool backward: 0 off, 1 large tensors, 2 always, 3 conditional-load form, 4 bf16 without the EXEC-mask routing") \
+  VN_OPT(pool_twalk,   1, "T-walking 3x3x3/s1 max-pool backward: 0 off, 1 large tensors, 2 always (any value above 3 too), 3 conditional-load form.  The forward's 8-channel T-walking kernel (kT 3, sT 1) reads it too: >= 2 forces it on small tensors, 0 does NOT switch it off") \
   VN_OPT(pool_blk,     1, "strided max-pool backward per 2x2 input block; 0 off") \
   VN_OPT(up_blk,       1, "8-channel upsample kernels (forward per 2x2 output block); 0 off") \
   VN_OPT(auc_ws,       0, "AUC-Judd sorts and counts in the caller's workspace whatever the number of fixations: 1 on (tests); 0 = in LDS up to 4096 fixations") \

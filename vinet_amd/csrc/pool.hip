@@ -1,5 +1,6 @@
 // MaxPool3d forward / backward kernels (model.py:696-714, model_utils.py:178): generic gathers, the packed-key 8-channel
-// forward, LDS halo-tile and T-walking 3x3x3/s1 kernels, the 2x2-block 1x3x3/s2 backward.
+// forward, LDS halo-tile and T-walking 3x3x3/s1 kernels, the 2x2-block 1x3x3/s2 backward.  The entry points are at the end
+// of the file: pool_fwd_route / pool_bwd_route decide the kernel, the launch and the name query read the same answer.
 #include "elementwise.h"
 
 // ============================================================================
@@ -17,6 +18,27 @@ static inline PoolP make_poolp(const VinetPoolDesc* d) {
 // agree with these fp32-compare kernels on every tie.
 template <typename T> VN_DEV float pool_round(float v) { return v; }
 template <> VN_DEV float pool_round<bf16_t>(float v) { return bf2f(f2bf(v)); }
+// ... on four channels from channel c
+template <typename T> VN_DEV float4 pool_pre4(float4 v, const Affine& pre, int c) {
+  v = affine4(v, pre, c);
+  if (pre.scale) { v.x = pool_round<T>(v.x); v.y = pool_round<T>(v.y); v.z = pool_round<T>(v.z); v.w = pool_round<T>(v.w); }
+  return v;
+}
+// ... on one element (sc = 1, sh = 0 without an affine)
+template <typename T> VN_DEV float pool_pre(float f, float sc, float sh, const Affine& pre) {
+  float v = fmaf(f, sc, sh);
+  if (pre.relu) v = fmaxf(v, 0.f);
+  if (pre.scale) v = pool_round<T>(v);
+  return v;
+}
+// (b, h, w) of the column a lane of a T-walking kernel owns
+VN_DEV void pool_column(const TView& v, uint32_t col, int& b, int& h, int& w) {
+  const uint32_t r1 = fdiv(col, v.dW);
+  w = (int)(col - r1 * (uint32_t)v.W);
+  const uint32_t r2 = fdiv(r1, v.dH);
+  h = (int)(r1 - r2 * (uint32_t)v.H);
+  b = (int)r2;
+}
 
 template <typename T>
 __global__ void maxpool_fwd_kernel(PoolP p, TView x, Affine pre, TView y, uint8_t* __restrict__ argmax, long total) {
@@ -38,9 +60,7 @@ __global__ void maxpool_fwd_kernel(PoolP p, TView x, Affine pre, TView y, uint8_
       for (int kw = 0; kw < p.kW; ++kw) {
         const int w = wo * p.sW - p.pW + kw;
         if ((unsigned)w >= (unsigned)x.W) continue;
-        float4 v = ldq<T>((const T*)x.p + vox_off(x, b, t, h, w) + q * 4);
-        v = affine4(v, pre, q * 4);
-        if (pre.scale) { v.x = pool_round<T>(v.x); v.y = pool_round<T>(v.y); v.z = pool_round<T>(v.z); v.w = pool_round<T>(v.w); }
+        const float4 v = pool_pre4<T>(ldq<T>((const T*)x.p + vox_off(x, b, t, h, w) + q * 4), pre, q * 4);
         const int tap = (kt * p.kH + kh) * p.kW + kw;
         const float f[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -63,11 +83,8 @@ __global__ void maxpool_tslide_kernel(PoolP p, TView x, Affine pre, TView y, uin
   if (i >= total) return;
   const uint32_t col = fdiv((uint32_t)i, y.dQ);
   const int q = (int)((uint32_t)i - col * (uint32_t)(y.C / 4));
-  const uint32_t r1 = fdiv(col, y.dW);
-  const int wo = (int)(col - r1 * (uint32_t)y.W);
-  const uint32_t r2 = fdiv(r1, y.dH);
-  const int ho = (int)(r1 - r2 * (uint32_t)y.H);
-  const int b = (int)r2;
+  int b, ho, wo;
+  pool_column(y, col, b, ho, wo);
   float pm[3][4];
   int pa[3][4];
   const int khw = p.kH * p.kW;
@@ -83,10 +100,10 @@ __global__ void maxpool_tslide_kernel(PoolP p, TView x, Affine pre, TView y, uin
         for (int kw = 0; kw < p.kW; ++kw) {
           const int w = wo * p.sW - p.pW + kw;
           if ((unsigned)w >= (unsigned)x.W) continue;
-          float4 v = ldq<T>((const T*)x.p + vox_off(x, b, tp, h, w) + q * 4);
-          v = affine4(v, pre, q * 4);
+          float4 v = pool_pre4<T>(ldq<T>((const T*)x.p + vox_off(x, b, tp, h, w) + q * 4), pre, q * 4);
+          // (rounded a second time: idempotent, so the results do not depend on it, but the compiler does not see that and
+          //  maxpool_tslide_kernel<bf16> is 12 instructions longer for it -- kept until a change that may alter kernel code)
           if (pre.scale) { v.x = pool_round<T>(v.x); v.y = pool_round<T>(v.y); v.z = pool_round<T>(v.z); v.w = pool_round<T>(v.w); }
-        if (pre.scale) { v.x = pool_round<T>(v.x); v.y = pool_round<T>(v.y); v.z = pool_round<T>(v.z); v.w = pool_round<T>(v.w); }
           const float f[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -161,9 +178,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd8_kernel(PoolP p, TView x, Aff
         const unsigned long long tap = (unsigned long long)((kt * p.kH + kh) * p.kW + kw);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          float v = fmaf(f[e], sc[e], sh[e]);
-          if (pre.relu) v = fmaxf(v, 0.f);
-          if (pre.scale) v = pool_round<T>(v);
+          const float v = pool_pre<T>(f[e], sc[e], sh[e], pre);
           if (v > best[e] || (v != v && best[e] == best[e])) { best[e] = v; bi = (bi & ~(0xffull << (8 * e))) | (tap << (8 * e)); }
         }
       }
@@ -184,11 +199,8 @@ __global__ __launch_bounds__(256) void maxpool_tslide8_kernel(PoolP p, TView x, 
   const int G = y.C >> 3;
   const uint32_t col = (uint32_t)(i / G);
   const int g = (int)(i - (long)col * G);
-  const uint32_t r1 = fdiv(col, y.dW);
-  const int wo = (int)(col - r1 * (uint32_t)y.W);
-  const uint32_t r2 = fdiv(r1, y.dH);
-  const int ho = (int)(r1 - r2 * (uint32_t)y.H);
-  const int b = (int)r2;
+  int b, ho, wo;
+  pool_column(y, col, b, ho, wo);
   float sc[8], sh[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { sc[e] = pre.scale ? pre.scale[g * 8 + e] : 1.f; sh[e] = pre.scale ? pre.shift[g * 8 + e] : 0.f; }
@@ -214,9 +226,7 @@ __global__ __launch_bounds__(256) void maxpool_tslide8_kernel(PoolP p, TView x, 
           const unsigned long long code = (unsigned long long)(kh * p.kW + kw);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            float v = fmaf(f[e], sc[e], sh[e]);
-            if (pre.relu) v = fmaxf(v, 0.f);
-            if (pre.scale) v = pool_round<T>(v);
+            const float v = pool_pre<T>(f[e], sc[e], sh[e], pre);
             if (v > m_c[e] || (v != v && m_c[e] == m_c[e])) { m_c[e] = v; i_c = (i_c & ~(0xffull << (8 * e))) | (code << (8 * e)); }
           }
         }
@@ -551,63 +561,6 @@ __global__ __launch_bounds__(512) void maxpool_k3s1_pk_kernel(TView x, Affine pr
   }
 }
 
-extern "C" int vinet_maxpool3d(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
-                               uint8_t* argmax, void* stream) {
-  VN_CHECK_ARG(d && x && y && quad_ok(*x, esize(d->dtype)) && quad_ok(*y, esize(d->dtype)) && x->C == y->C && x->B == y->B,
-               "maxpool3d: bad views");
-  VN_CHECK_ARG(d->kT * d->kH * d->kW <= 255 && d->kT > 0 && d->kH > 0 && d->kW > 0, "maxpool3d: window too large");
-  const PoolP p = make_poolp(d);
-  const bool k3s1 = d->kT == 3 && d->kH == 3 && d->kW == 3 && d->sT == 1 && d->sH == 1 && d->sW == 1 && d->pT == 1 && d->pH == 1 &&
-                    d->pW == 1 && y->T == x->T && y->H == x->H && y->W == x->W;
-  if (k3s1 && g_vinet_opt_pool_lds && x->T >= 2 && oct_ok(*x) && oct_ok(*y) && (!argmax || ((uintptr_t)argmax % 8) == 0) &&
-      (g_vinet_opt_pool_lds >= 2 || (long)y->B * y->H * y->W * (y->C / 8) >= 65536)) {
-    const int tilesH = (y->H + 7) / 8, tilesW = (y->W + 7) / 8;
-    const long blocks = (long)y->B * tilesH * tilesW * ((y->C + 63) / 64);
-    const bool pre_ok = !pre.scale || pre.shift;
-    if (d->dtype == VINET_BF16 && g_vinet_opt_pool_pk && pre_ok && x->ld % 8 == 0 && ((uintptr_t)x->ptr % 16) == 0 && ((uintptr_t)y->ptr % 16) == 0 &&
-        x->sB % 8 == 0 && y->sB % 8 == 0) {
-      hipLaunchKernelGGL(maxpool_k3s1_pk_kernel, dim3((unsigned)blocks), dim3(512), 0, (hipStream_t)stream, make_view(*x),
-                         make_affine(pre), make_view(*y), argmax, tilesH, tilesW);
-      return vn_launch_status("maxpool3d(k3s1 packed keys)");
-    }
-    DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_k3s1_lds_kernel<T>, dim3((unsigned)blocks), dim3(512), 0, (hipStream_t)stream,
-                                               make_view(*x), make_affine(pre), make_view(*y), argmax, tilesH, tilesW);)
-    return vn_launch_status("maxpool3d(k3s1 lds)");
-  }
-  if (d->kT == 3 && d->sT == 1 && d->pT == 1 && y->T == x->T && x->T >= 2 && oct_ok(*x) && oct_ok(*y) &&
-      (!argmax || ((uintptr_t)argmax % 8) == 0) &&
-      (g_vinet_opt_pool_twalk >= 2 || (long)y->B * y->H * y->W * (y->C / 8) >= 65536)) {
-    // (fewer columns than that cannot fill the chip while each lane walks T serially: batch-1 inference
-    //  takes the one-thread-per-output kernel below)
-    const long cols8 = (long)y->B * y->H * y->W * (y->C / 8);
-    DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_tslide8_kernel<T>, dim3(ew_grid(cols8)), dim3(256), 0,
-                                               (hipStream_t)stream, p, make_view(*x), make_affine(pre), make_view(*y), argmax, cols8);)
-    return vn_launch_status("maxpool3d(tslide8)");
-  }
-  if (d->kT == 3 && d->sT == 1 && d->pT == 1 && y->T == x->T && x->T >= 2 && !(oct_ok(*x) && oct_ok(*y))) {
-    const long cols = (long)y->B * y->H * y->W * (y->C / 4);
-    DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_tslide_kernel<T>, dim3(ew_grid(cols)), dim3(256), 0,
-                                               (hipStream_t)stream, p, make_view(*x), make_affine(pre), make_view(*y), argmax, cols);)
-    return vn_launch_status("maxpool3d(tslide)");
-  }
-  if (oct_ok(*x) && oct_ok(*y) && (!argmax || ((uintptr_t)argmax % 8) == 0)) {
-    const long total8 = view_voxels(*y) * (y->C / 8);
-    if (d->dtype == VINET_BF16 && g_vinet_opt_pool_pk && (!pre.scale || pre.shift) && ((uintptr_t)x->ptr % 16) == 0 && ((uintptr_t)y->ptr % 16) == 0 &&
-        x->sB % 8 == 0 && y->sB % 8 == 0) {
-      hipLaunchKernelGGL(maxpool_fwd8_pk_kernel, dim3(ew_grid(total8)), dim3(256), 0, (hipStream_t)stream, p, make_view(*x),
-                         make_affine(pre), make_view(*y), argmax, total8);
-      return vn_launch_status("maxpool3d(8, packed keys)");
-    }
-    DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_fwd8_kernel<T>, dim3(ew_grid(total8)), dim3(256), 0,
-                                               (hipStream_t)stream, p, make_view(*x), make_affine(pre), make_view(*y), argmax, total8);)
-    return vn_launch_status("maxpool3d(8)");
-  }
-  const long total = view_voxels(*y) * (y->C / 4);
-  DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(ew_grid(total)), dim3(256), 0,
-                                             (hipStream_t)stream, p, make_view(*x), make_affine(pre), make_view(*y), argmax, total);)
-  return vn_launch_status("maxpool3d");
-}
-
 // g += v in the lanes whose code byte (byte BYTE of `word`) equals `code`: v_cmpx (SDWA byte select) -> add under EXEC -> EXEC restored
 #define POOL_ADD_IF_X(g, word, BYTE, code, v, exec0)                                                                                  \
   asm volatile("v_cmpx_eq_u32_sdwa vcc, %1, %2 src0_sel:BYTE_" #BYTE " src1_sel:DWORD\n\tv_add_f32_e32 %0, %0, %3\n\ts_mov_b64 exec, %4" \
@@ -930,11 +883,8 @@ __global__ __launch_bounds__(256) void maxpool_bwd_k3s1_twalk_kernel(TView dy, c
   const int G = dx.C >> 3;
   const uint32_t col = (uint32_t)(i / G);
   const int g = (int)(i - (long)col * G);
-  const uint32_t r1 = fdiv(col, dx.dW);
-  const int w = (int)(col - r1 * (uint32_t)dx.W);
-  const uint32_t r2 = fdiv(r1, dx.dH);
-  const int h = (int)(r1 - r2 * (uint32_t)dx.H);
-  const int b = (int)r2;
+  int b, h, w;
+  pool_column(dx, col, b, h, w);
   const int T_ = dx.T, H = dx.H, W = dx.W;
   float g_m[8], g_0[8], g_p[8];      // gradients of inputs to-1, to, to+1 while output plane `to` is processed
 #pragma unroll
@@ -991,83 +941,10 @@ __global__ __launch_bounds__(256) void maxpool_bwd_k3s1_twalk_kernel(TView dy, c
 // Same walk for bf16 with every load of a plane issued up front: the 9 argmax words AND the 9 gradient vectors of the
 // in-plane neighbour windows are fetched unconditionally (they are L1 / L2 hits for 8 of 9 lanes), 18 independent loads
 // per lane and plane, so a lane pays one memory latency per plane instead of two dependent ones
-// (the conditional gradient loads of the form above left the kernel latency-bound at 1.4 TB/s).  Routing is branch-free:
-// byte code - (kh*3+kw) is 0 / 9 / 18 for the temporal taps to-1 / to / to+1.
-__global__ __launch_bounds__(256) void maxpool_bwd_k3s1_tw2_kernel(TView dy, const uint8_t* __restrict__ argmax, TView dx,
-                                                                   int accumulate, long total) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int G = dx.C >> 3;
-  const uint32_t col = (uint32_t)(i / G);
-  const int g = (int)(i - (long)col * G);
-  const uint32_t r1 = fdiv(col, dx.dW);
-  const int w = (int)(col - r1 * (uint32_t)dx.W);
-  const uint32_t r2 = fdiv(r1, dx.dH);
-  const int h = (int)(r1 - r2 * (uint32_t)dx.H);
-  const int b = (int)r2;
-  const int T_ = dx.T, H = dx.H, W = dx.W;
-  // lane-relative addresses of the 9 windows (the lane's own voxel where the window does not exist: any valid address)
-  const uint8_t* amp = argmax + ((((long)b * T_) * H + h) * W + w) * (long)dx.C + g * 8;
-  const unsigned short* dyp = (const unsigned short*)dy.p + vox_off(dy, b, 0, h, w) + g * 8;
-  const long am_plane = (long)H * W * dx.C, dy_plane = (long)H * W * dy.ld;
-  uint32_t okmask = 0;
-#pragma unroll
-  for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-      const int ho = h + 1 - kh, wo = w + 1 - kw;
-      okmask |= (((unsigned)ho < (unsigned)H && (unsigned)wo < (unsigned)W) ? 1u : 0u) << (kh * 3 + kw);
-    }
-  float g_m[8], g_0[8], g_p[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { g_m[e] = 0.f; g_0[e] = 0.f; g_p[e] = 0.f; }
-  for (int to = 0; to <= T_; ++to) {
-    if (to < T_) {
-      unsigned long long am[9];
-      uint4 dv[9];
-#pragma unroll
-      for (int s = 0; s < 9; ++s) {
-        const int dvox = (1 - s / 3) * W + (1 - s % 3);
-        const bool ok = (okmask >> s) & 1u;
-        am[s] = *(const unsigned long long*)(amp + (ok ? dvox * dx.C : 0));
-        dv[s] = *(const uint4*)(dyp + (ok ? dvox * dy.ld : 0));
-      }
-#pragma unroll
-      for (int s = 0; s < 9; ++s) {
-        const unsigned long long a = ((okmask >> s) & 1u) ? am[s] : ~0ull;
-        const uint32_t alo = (uint32_t)a, ahi = (uint32_t)(a >> 32);
-        const uint32_t q[4] = {dv[s].x, dv[s].y, dv[s].z, dv[s].w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const uint32_t c = (((e < 4) ? alo : ahi) >> (8 * (e & 3))) & 0xffu;
-          const int dlt = (int)c - s;
-          const float v = (e & 1) ? __uint_as_float(q[e >> 1] & 0xffff0000u) : __uint_as_float(q[e >> 1] << 16);
-          g_m[e] += (dlt == 0) ? v : 0.f;
-          g_0[e] += (dlt == 9) ? v : 0.f;
-          g_p[e] += (dlt == 18) ? v : 0.f;
-        }
-      }
-      amp += am_plane;
-      dyp += dy_plane;
-    }
-    const int t = to - 1;
-    if (t >= 0) {
-      unsigned short* dst = (unsigned short*)dx.p + vox_off(dx, b, t, h, w) + g * 8;
-      if (accumulate) {
-        float o[8];
-        ld8<unsigned short>(dst, o);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g_m[e] += o[e];
-      }
-      st8<unsigned short>(dst, g_m);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { g_m[e] = g_0[e]; g_0[e] = g_p[e]; g_p[e] = 0.f; }
-  }
-}
-
-// the same walk with the routing done on the EXEC mask: 1127 -> 836 VALU instructions per plane and lane, 3.01 -> 2.37 ms on the
-// 256-channel pool at 28 x 48 (the default; pool_twalk = 4 selects the form above)
+// (the conditional gradient loads of the form above left the kernel latency-bound at 1.4 TB/s).  The byte code of window s is
+// s / s + 9 / s + 18 for the temporal taps to-1 / to / to+1, and the routing is done on the EXEC mask (POOL_ADD_IF): against
+// compare + select + add per (window, channel, temporal tap) that is 1127 -> 836 VALU instructions per plane and lane and
+// 3.01 -> 2.37 ms on the 256-channel pool at 28 x 48 -- the reason for the inline asm.
 __global__ __launch_bounds__(256) void maxpool_bwd_k3s1_tw3_kernel(TView dy, const uint8_t* __restrict__ argmax, TView dx,
                                                                    int accumulate, long total) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1077,11 +954,8 @@ __global__ __launch_bounds__(256) void maxpool_bwd_k3s1_tw3_kernel(TView dy, con
   const int G = dx.C >> 3;
   const uint32_t col = (uint32_t)(i / G);
   const int g = (int)(i - (long)col * G);
-  const uint32_t r1 = fdiv(col, dx.dW);
-  const int w = (int)(col - r1 * (uint32_t)dx.W);
-  const uint32_t r2 = fdiv(r1, dx.dH);
-  const int h = (int)(r1 - r2 * (uint32_t)dx.H);
-  const int b = (int)r2;
+  int b, h, w;
+  pool_column(dx, col, b, h, w);
   const int T_ = dx.T, H = dx.H, W = dx.W;
   // lane-relative addresses of the 9 windows (the lane's own voxel where the window does not exist: any valid address)
   const uint8_t* amp = argmax + ((((long)b * T_) * H + h) * W + w) * (long)dx.C + g * 8;
@@ -1147,60 +1021,164 @@ __global__ __launch_bounds__(256) void maxpool_bwd_k3s1_tw3_kernel(TView dy, con
   }
 }
 
-extern "C" int vinet_maxpool3d_bwd(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax,
-                                   const VinetTensor* dx, int32_t accumulate, void* stream) {
+// ============================================================================
+// Routes: which kernel a pool runs, decided once per entry point
+// ============================================================================
+enum PoolKind { POOL_FWD, POOL_TSLIDE, POOL_FWD8, POOL_FWD8_PK, POOL_TSLIDE8, POOL_K3S1_LDS, POOL_K3S1_PK,
+                POOL_BWD, POOL_BWD8, POOL_BWD_K133S2, POOL_BWD_K3S2, POOL_BWD_K3S1, POOL_BWD_K3S1_TWALK, POOL_BWD_K3S1_TW3 };
+struct PoolRoute {
+  PoolKind kind;
+  const char* name;      // the kernel's symbol; `typed`: a template over the activation dtype
+  bool typed;
+  long n;                // lanes of the launch (the two LDS kernels: workgroups)
+  int tilesH, tilesW;    // LDS kernels: 8 x 8 output tiles of a plane
+  int TB, HB, WB;        // block backward kernels: blocks of two input voxels per dimension
+};
+
+// fewer 8-channel columns than this cannot fill the chip while each lane walks T serially: batch-1 inference takes the
+// one-thread-per-output kernels
+static const long POOL_FILL_COLS = 65536;
+
+// the 3x3x3 / s1 / p1 pool of the Inception branches (model_utils.py:178)
+static bool pool_is_k3s1(const VinetPoolDesc* d, const VinetTensor& a, const VinetTensor& b) {
+  return d->kT == 3 && d->kH == 3 && d->kW == 3 && d->sT == 1 && d->sH == 1 && d->sW == 1 && d->pT == 1 && d->pH == 1 && d->pW == 1 &&
+         a.T == b.T && a.H == b.H && a.W == b.W;
+}
+// 8 channels per lane: 16-byte bf16 accesses on both tensors, the 8 argmax codes as one word (a null argmax -- inference -- passes)
+static bool pool_oct(const VinetTensor& a, const VinetTensor& b, const uint8_t* argmax) {
+  return oct_ok(a) && oct_ok(b) && ((uintptr_t)argmax % 8) == 0;
+}
+
+static PoolRoute pool_fwd_route(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y, const uint8_t* argmax) {
+  const bool oct = pool_oct(*x, *y, argmax);
+  const bool walk_t = d->kT == 3 && d->sT == 1 && d->pT == 1 && y->T == x->T && x->T >= 2;      // T-walking kernels: any in-plane window
+  const bool pk = d->dtype == VINET_BF16 && g_vinet_opt_pool_pk && (!pre.scale || pre.shift);      // bf16 on packed keys
+  const long cols8 = (long)y->B * y->H * y->W * (y->C / 8);
+  if (pool_is_k3s1(d, *x, *y) && walk_t && oct && g_vinet_opt_pool_lds && (g_vinet_opt_pool_lds >= 2 || cols8 >= POOL_FILL_COLS)) {
+    const int tilesH = (y->H + 7) / 8, tilesW = (y->W + 7) / 8;
+    const long blocks = (long)y->B * tilesH * tilesW * ((y->C + 63) / 64);
+    if (pk) return {POOL_K3S1_PK, "maxpool_k3s1_pk_kernel", false, blocks, tilesH, tilesW};
+    return {POOL_K3S1_LDS, "maxpool_k3s1_lds_kernel", true, blocks, tilesH, tilesW};
+  }
+  // quirk, kept: the BACKWARD's option forces this forward kernel on small tensors (pool_twalk >= 2), and pool_twalk = 0 does not switch it off
+  if (walk_t && oct && (g_vinet_opt_pool_twalk >= 2 || cols8 >= POOL_FILL_COLS)) return {POOL_TSLIDE8, "maxpool_tslide8_kernel", true, cols8};
+  // quirk, kept: the 4-channel T-walk has no size gate, and a misaligned argmax alone (tensors fine) goes to maxpool_fwd_kernel instead
+  if (walk_t && !(oct_ok(*x) && oct_ok(*y))) return {POOL_TSLIDE, "maxpool_tslide_kernel", true, (long)y->B * y->H * y->W * (y->C / 4)};
+  if (oct) {
+    const long total8 = view_voxels(*y) * (y->C / 8);
+    if (pk) return {POOL_FWD8_PK, "maxpool_fwd8_pk_kernel", false, total8};
+    return {POOL_FWD8, "maxpool_fwd8_kernel", true, total8};
+  }
+  return {POOL_FWD, "maxpool_fwd_kernel", true, view_voxels(*y) * (y->C / 4)};
+}
+
+static PoolRoute pool_bwd_route(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax, const VinetTensor* dx) {
+  const bool oct = pool_oct(*dx, *dy, argmax);
+  const long total8 = view_voxels(*dx) * (dx->C / 8);
+  if (oct && pool_is_k3s1(d, *dx, *dy)) {
+    const long cols8 = (long)dx->B * dx->H * dx->W * (dx->C / 8);
+    if (g_vinet_opt_pool_twalk >= 2 || (g_vinet_opt_pool_twalk && cols8 >= POOL_FILL_COLS)) {      // 2: force (tests); above 3: as 2
+      // bf16 issues every load up front unless pool_twalk = 3 asks for the conditional-load form (A/B); its in-plane offsets are 32-bit
+      if (g_vinet_opt_pool_twalk != 3 && d->dtype == VINET_BF16 && (long)dx->H * dx->W * dx->C < (1l << 30) &&
+          (long)dx->H * dx->W * dy->ld < (1l << 30))
+        return {POOL_BWD_K3S1_TW3, "maxpool_bwd_k3s1_tw3_kernel", false, cols8};
+      return {POOL_BWD_K3S1_TWALK, "maxpool_bwd_k3s1_twalk_kernel", true, cols8};
+    }
+    return {POOL_BWD_K3S1, "maxpool_bwd_k3s1_kernel", true, total8};
+  }
+  if (oct && g_vinet_opt_pool_blk && d->kH == 3 && d->kW == 3 && d->sH == 2 && d->sW == 2 && d->pH == 1 && d->pW == 1 &&
+      dy->H == (dx->H - 1) / 2 + 1 && dy->W == (dx->W - 1) / 2 + 1) {      // one lane per 2 x 2 (x 2) input block
+    const int TB = (dx->T + 1) / 2, HB = (dx->H + 1) / 2, WB = (dx->W + 1) / 2;
+    if (d->kT == 1 && d->sT == 1 && d->pT == 0 && dy->T == dx->T)
+      return {POOL_BWD_K133S2, "maxpool_bwd_k133s2_kernel", true, (long)dx->B * dx->T * HB * WB * (dx->C / 8), 0, 0, 0, HB, WB};
+    if (d->kT == 3 && d->sT == 2 && d->pT == 1 && dy->T == (dx->T - 1) / 2 + 1)
+      return {POOL_BWD_K3S2, "maxpool_bwd_k3s2_kernel", true, (long)dx->B * TB * HB * WB * (dx->C / 8), 0, 0, TB, HB, WB};
+  }
+  if (oct) return {POOL_BWD8, "maxpool_bwd8_kernel", true, total8};
+  return {POOL_BWD, "maxpool_bwd_kernel", true, view_voxels(*dx) * (dx->C / 4)};
+}
+
+static int pool_fwd_args(const VinetPoolDesc* d, const VinetTensor* x, const VinetTensor* y) {
+  VN_CHECK_ARG(d && x && y && quad_ok(*x, esize(d->dtype)) && quad_ok(*y, esize(d->dtype)) && x->C == y->C && x->B == y->B,
+               "maxpool3d: bad views");
+  VN_CHECK_ARG(d->kT * d->kH * d->kW <= 255 && d->kT > 0 && d->kH > 0 && d->kW > 0, "maxpool3d: window too large");
+  return 0;
+}
+static int pool_bwd_args(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax, const VinetTensor* dx) {
   VN_CHECK_ARG(d && dy && dx && argmax && quad_ok(*dy, esize(d->dtype)) && quad_ok(*dx, esize(d->dtype)) &&
                    dx->C == dy->C && dx->B == dy->B, "maxpool3d_bwd: bad views");
+  return 0;
+}
+// "maxpool_fwd8_kernel<bf16>", "maxpool_k3s1_pk_kernel": the symbol, with the dtype DISPATCH_T instantiates it for
+static int pool_kernel_name(const PoolRoute& r, int dtype, char* buf, int32_t n) {
+  snprintf(buf, n, r.typed ? "%s<%s>" : "%s", r.name, dtype == VINET_F32 ? "f32" : "bf16");
+  return 0;
+}
+
+extern "C" int vinet_maxpool3d_kernel_name(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
+                                           const uint8_t* argmax, char* buf, int32_t n) {
+  if (!buf || n <= 0 || pool_fwd_args(d, x, y)) return -1;
+  return pool_kernel_name(pool_fwd_route(d, x, pre, y, argmax), d->dtype, buf, n);
+}
+extern "C" int vinet_maxpool3d_bwd_kernel_name(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax,
+                                               const VinetTensor* dx, char* buf, int32_t n) {
+  if (!buf || n <= 0 || pool_bwd_args(d, dy, argmax, dx)) return -1;
+  return pool_kernel_name(pool_bwd_route(d, dy, argmax, dx), d->dtype, buf, n);
+}
+
+extern "C" int vinet_maxpool3d(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
+                               uint8_t* argmax, void* stream) {
+  if (pool_fwd_args(d, x, y)) return -1;
+  const PoolRoute r = pool_fwd_route(d, x, pre, y, argmax);
   const PoolP p = make_poolp(d);
-  const bool k3s1 = d->kT == 3 && d->kH == 3 && d->kW == 3 && d->sT == 1 && d->sH == 1 && d->sW == 1 && d->pT == 1 && d->pH == 1 &&
-                    d->pW == 1 && dy->T == dx->T && dy->H == dx->H && dy->W == dx->W;
-  if (k3s1 && dx->C % 8 == 0 && dx->ld % 8 == 0 && dy->ld % 8 == 0 && dx->sB % 8 == 0 && dy->sB % 8 == 0 &&
-      ((uintptr_t)dx->ptr % 16) == 0 && ((uintptr_t)dy->ptr % 16) == 0 && ((uintptr_t)argmax % 8) == 0) {
-    const long cols8 = (long)dx->B * dx->H * dx->W * (dx->C / 8);
-    if (g_vinet_opt_pool_twalk != 3 && d->dtype == VINET_BF16 && (g_vinet_opt_pool_twalk >= 2 || (g_vinet_opt_pool_twalk && cols8 >= 65536)) &&
-        (long)dx->H * dx->W * dx->C < (1l << 30) && (long)dx->H * dx->W * dy->ld < (1l << 30)) {   // 3: the conditional-load form (A/B)
-      if (g_vinet_opt_pool_twalk != 4)      // (4: the compare / select / add form, for A/B and tests)
-        hipLaunchKernelGGL(maxpool_bwd_k3s1_tw3_kernel, dim3(ew_grid(cols8)), dim3(256), 0, (hipStream_t)stream, make_view(*dy), argmax,
-                           make_view(*dx), accumulate, cols8);
-      else
-        hipLaunchKernelGGL(maxpool_bwd_k3s1_tw2_kernel, dim3(ew_grid(cols8)), dim3(256), 0, (hipStream_t)stream, make_view(*dy), argmax,
-                           make_view(*dx), accumulate, cols8);
-      return vn_launch_status("maxpool3d_bwd(k3s1 tw2)");
-    }
-    if (g_vinet_opt_pool_twalk >= 2 || (g_vinet_opt_pool_twalk && cols8 >= 65536)) {   // 2: force (tests)   // enough columns to fill the chip
-      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_k3s1_twalk_kernel<T>, dim3(ew_grid(cols8)), dim3(256), 0,
-                                                 (hipStream_t)stream, make_view(*dy), argmax, make_view(*dx), accumulate, cols8);)
-      return vn_launch_status("maxpool3d_bwd(k3s1 twalk)");
-    }
-    const long total8 = view_voxels(*dx) * (dx->C / 8);
-    DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_k3s1_kernel<T>, dim3(ew_grid(total8)), dim3(256), 0, (hipStream_t)stream,
-                                               make_view(*dy), argmax, make_view(*dx), accumulate, total8);)
-    return vn_launch_status("maxpool3d_bwd(k3s1)");
+  const TView xv = make_view(*x), yv = make_view(*y);
+  const Affine a = make_affine(pre);
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 lanes(256), grid(r.kind == POOL_K3S1_PK || r.kind == POOL_K3S1_LDS ? (unsigned)r.n : ew_grid(r.n));
+  switch (r.kind) {
+    case POOL_K3S1_PK: hipLaunchKernelGGL(maxpool_k3s1_pk_kernel, grid, dim3(512), 0, s, xv, a, yv, argmax, r.tilesH, r.tilesW); break;
+    case POOL_K3S1_LDS:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_k3s1_lds_kernel<T>, grid, dim3(512), 0, s, xv, a, yv, argmax,
+                                                 r.tilesH, r.tilesW);) break;
+    case POOL_TSLIDE8:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_tslide8_kernel<T>, grid, lanes, 0, s, p, xv, a, yv, argmax, r.n);) break;
+    case POOL_TSLIDE:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_tslide_kernel<T>, grid, lanes, 0, s, p, xv, a, yv, argmax, r.n);) break;
+    case POOL_FWD8_PK: hipLaunchKernelGGL(maxpool_fwd8_pk_kernel, grid, lanes, 0, s, p, xv, a, yv, argmax, r.n); break;
+    case POOL_FWD8:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_fwd8_kernel<T>, grid, lanes, 0, s, p, xv, a, yv, argmax, r.n);) break;
+    case POOL_FWD:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_fwd_kernel<T>, grid, lanes, 0, s, p, xv, a, yv, argmax, r.n);) break;
+    default: break;      // (the backward's kinds: pool_fwd_route never answers them)
   }
-  if (oct_ok(*dx) && oct_ok(*dy) && ((uintptr_t)argmax % 8) == 0) {
-    const long total8 = view_voxels(*dx) * (dx->C / 8);
-    if (g_vinet_opt_pool_blk && d->kT == 1 && d->sT == 1 && d->pT == 0 && d->kH == 3 && d->kW == 3 && d->sH == 2 && d->sW == 2 && d->pH == 1 &&
-        d->pW == 1 && dy->T == dx->T && dy->H == (dx->H - 1) / 2 + 1 && dy->W == (dx->W - 1) / 2 + 1) {
-      const int HB = (dx->H + 1) / 2, WB = (dx->W + 1) / 2;
-      const long nthr = (long)dx->B * dx->T * HB * WB * (dx->C / 8);
-      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_k133s2_kernel<T>, dim3(ew_grid(nthr)), dim3(256), 0, (hipStream_t)stream,
-                                                 make_view(*dy), argmax, make_view(*dx), accumulate, HB, WB, nthr);)
-      return vn_launch_status("maxpool3d_bwd(k133s2)");
-    }
-    if (g_vinet_opt_pool_blk && d->kT == 3 && d->kH == 3 && d->kW == 3 && d->sT == 2 && d->sH == 2 && d->sW == 2 && d->pT == 1 && d->pH == 1 &&
-        d->pW == 1 && dy->T == (dx->T - 1) / 2 + 1 && dy->H == (dx->H - 1) / 2 + 1 && dy->W == (dx->W - 1) / 2 + 1) {
-      const int TB = (dx->T + 1) / 2, HB = (dx->H + 1) / 2, WB = (dx->W + 1) / 2;
-      const long nthr = (long)dx->B * TB * HB * WB * (dx->C / 8);
-      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_k3s2_kernel<T>, dim3(ew_grid(nthr)), dim3(256), 0, (hipStream_t)stream,
-                                                 make_view(*dy), argmax, make_view(*dx), accumulate, TB, HB, WB, nthr);)
-      return vn_launch_status("maxpool3d_bwd(k3s2)");
-    }
-    DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd8_kernel<T>, dim3(ew_grid(total8)), dim3(256), 0, (hipStream_t)stream,
-                                               p, make_view(*dy), argmax, make_view(*dx), accumulate, total8);)
-    return vn_launch_status("maxpool3d_bwd8");
+  return vn_launch_status(r.name);
+}
+
+extern "C" int vinet_maxpool3d_bwd(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax,
+                                   const VinetTensor* dx, int32_t accumulate, void* stream) {
+  if (pool_bwd_args(d, dy, argmax, dx)) return -1;
+  const PoolRoute r = pool_bwd_route(d, dy, argmax, dx);
+  const PoolP p = make_poolp(d);
+  const TView gv = make_view(*dy), xv = make_view(*dx);
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 lanes(256), grid(ew_grid(r.n));
+  switch (r.kind) {
+    case POOL_BWD_K3S1_TW3: hipLaunchKernelGGL(maxpool_bwd_k3s1_tw3_kernel, grid, lanes, 0, s, gv, argmax, xv, accumulate, r.n); break;
+    case POOL_BWD_K3S1_TWALK:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_k3s1_twalk_kernel<T>, grid, lanes, 0, s, gv, argmax, xv, accumulate, r.n);) break;
+    case POOL_BWD_K3S1:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_k3s1_kernel<T>, grid, lanes, 0, s, gv, argmax, xv, accumulate, r.n);) break;
+    case POOL_BWD_K133S2:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_k133s2_kernel<T>, grid, lanes, 0, s, gv, argmax, xv, accumulate,
+                                                 r.HB, r.WB, r.n);) break;
+    case POOL_BWD_K3S2:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_k3s2_kernel<T>, grid, lanes, 0, s, gv, argmax, xv, accumulate,
+                                                 r.TB, r.HB, r.WB, r.n);) break;
+    case POOL_BWD8:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd8_kernel<T>, grid, lanes, 0, s, p, gv, argmax, xv, accumulate, r.n);) break;
+    case POOL_BWD:
+      DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_kernel<T>, grid, lanes, 0, s, p, gv, argmax, xv, accumulate, r.n);) break;
+    default: break;      // (the forward's kinds: pool_bwd_route never answers them)
   }
-  const long total = view_voxels(*dx) * (dx->C / 4);
-  DISPATCH_T(d->dtype, T, hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(ew_grid(total)), dim3(256), 0,
-                                             (hipStream_t)stream, p, make_view(*dy), argmax, make_view(*dx), accumulate, total);)
-  return vn_launch_status("maxpool3d_bwd");
+  return vn_launch_status(r.name);
 }
