@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VINET_ABI_VERSION 16   /* still 16: vinet_auc_borji, vinet_auc_borji_workspace and vinet_info_gain are pure additions (no existing entry point or struct changed); 16: vinet_auc_shuffled, vinet_auc_shuffled_workspace; 15: vinet_transformer_fwd / _bwd / _workspace; 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
+#define VINET_ABI_VERSION 16   /* still 16: vinet_emd, vinet_emd_hist and vinet_emd_workspace are pure additions as well; vinet_auc_borji, vinet_auc_borji_workspace and vinet_info_gain are pure additions (no existing entry point or struct changed); 16: vinet_auc_shuffled, vinet_auc_shuffled_workspace; 15: vinet_transformer_fwd / _bwd / _workspace; 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
 
 enum { VINET_F32 = 0, VINET_BF16 = 1,
        /* conv / weight-gradient descriptors only: fp32 tensors (as VINET_F32), bf16 matrix arithmetic on a two-term split of both
@@ -483,6 +483,35 @@ int vinet_auc_borji(const void* s, int32_t s_is_f64, const void* fix, int32_t fi
 int vinet_info_gain(const void* s, int32_t s_is_f64, const void* fix, int32_t fix_is_f64, const void* baseline,
                     int32_t baseline_is_f64, int64_t baseline_stride, int32_t B, int32_t n, double* score, int32_t* nfix,
                     void* stream);
+
+/* ------------------------------------------------------------------------
+ * Earth mover's distance (code_for_Metrics/EMD.m with FastEMD's emd_hat_gd_metric, extra mass penalty 0).  Forward only.
+ * vinet_emd_hist scores ready histograms: P, Q fp64 [B][R*C], the bins of an R x C grid in row-major order, D the Euclidean
+ * distance of the bin centres.  As the reference's double wrapper does: m = min(P, Q) per bin is pre-flowed (p = P - m,
+ * q = Q - m, negative bins included), ip = floor(p f + 0.5), iq = floor(q f + 0.5), iC = floor(D cf + 0.5) with
+ * f = 1e6 / max(sum P, sum Q) (running sums in bin order) and cf = 1e6 / max D; the side with the larger integer sum supplies;
+ * K = the minimum of sum flow * iC that ships every unit of the lighter side, the surplus dropped free; score[b] = K / f / cf.
+ * cost[b] = K (optional, int64; -1 with a non-zero status) and status[b] (optional, int32): 0, or 1 the augmentation guard
+ * was reached, 2 / 3 an internal inconsistency, 4 more than 2^31 - 1 units of mass -- each with a NaN score.  The score is
+ * also NaN, with status 0 and cost 0, when max(sum P, sum Q) is not positive and finite (a NaN bin included) or the grid has one bin.
+ * vinet_emd starts from the maps: `gt` [B][Hg][Wg] and `s` [B][Hs][Ws], fp32 or fp64, each resized to R x C by the two weight
+ * matrices given for it -- fp64, dense, [R][Hg] and [C][Wg] for gt, [R][Hs] and [C][Ws] for s; MATLAB's imresize weights are
+ * what vinet_amd.utils.matlab_resize_weights builds -- out[r][c] = sum_w wc[c][w] sum_h wr[r][h] x[h][w], then divided by its
+ * sum; P comes from gt, Q from s.  R = ceil(Hg / downsize), C = ceil(Wg / downsize) is checked.  hist_out (optional, fp64
+ * [B][2][R*C]) receives P and Q.  A resized map whose sum is zero or that holds a NaN gives NaN.
+ * The solver is exact (successive shortest paths on the integers; sums in a fixed order): a map's score and cost are
+ * bit-identical alone and in any batch.  At most 512 bins (EMD_MAX_BINS: 12 x 20 = 240 for a 360 x 640 map at downsize 32,
+ * 17 x 30 = 510 for 1080 x 1920 at 64): the flow matrix takes up to (bins / 2)^2 int32 of workspace per map, and the guard on the
+ * solver's loops, (16 n + 16)(n + 1) Dijkstra rounds for n <= bins nodes, stays at seconds.  More bins, downsize < 1, R * C < 1
+ * are refused before any launch.  `workspace` must hold vinet_emd_workspace(B, R, C) bytes, 8-byte aligned (0 = invalid arguments).
+ * ---------------------------------------------------------------------- */
+size_t vinet_emd_workspace(int32_t B, int32_t R, int32_t C);
+int vinet_emd(const void* s, int32_t s_is_f64, int32_t Hs, int32_t Ws, const void* gt, int32_t gt_is_f64, int32_t Hg, int32_t Wg,
+              int32_t B, int32_t downsize, int32_t R, int32_t C, const double* w_gt_r, const double* w_gt_c, const double* w_s_r,
+              const double* w_s_c, void* workspace, size_t workspace_bytes, double* score, int64_t* cost, int32_t* status,
+              double* hist_out, void* stream);
+int vinet_emd_hist(const double* P, const double* Q, int32_t B, int32_t R, int32_t C, void* workspace, size_t workspace_bytes,
+                   double* score, int64_t* cost, int32_t* status, void* stream);
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) over one flat fp32 buffer
  * (train.py:188,217). bias corrections are passed by the host. */

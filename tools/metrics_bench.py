@@ -10,7 +10,11 @@ locations (a frame against its video's union map), 100 splits, step 0.1, the dev
 model of that draw.  AUC-Borji and information-gain rows (`--borji 0` / `--ig 0` leave them out): the same shapes; AUC-Borji with
 100 splits, step 0.1, the device draw; the information gain with one baseline map for the batch.  Every shape is warmed up; a timing is a host clock around `reps` calls that end in a device
 synchronise.  `--forward 1` also times the ViNet-32 forward (bf16, 224x384) that produces 64 maps, the yardstick the metric
-should stay below.  No GPU: the device columns fail, nothing falls back.
+should stay below.  EMD rows (`--emd 0` leaves them out): `loss.emd_batch` end to end and `loss.emd_hist_batch` (the solver alone)
+at 7x12 bins (224x384 maps) and 12x20 bins (360x640) at downsize 32, B = 64 and 256, eight different map pairs repeated over the
+batch; the host column is not a model but the CPU time of the reference's own solver on a dense histogram of that grid, as
+tests/golden/make_emd_goldens.py recorded it (one core).  `--judd 0` leaves the AUC-Judd rows out.  No GPU: the device columns
+fail, nothing falls back.
 """
 import argparse
 import json
@@ -57,11 +61,13 @@ def main():
     p.add_argument("--sauc", default=1, type=int)
     p.add_argument("--borji", default=1, type=int)
     p.add_argument("--ig", default=1, type=int)
+    p.add_argument("--emd", default=1, type=int)
+    p.add_argument("--judd", default=1, type=int)
     args = p.parse_args()
     assert torch.cuda.is_available(), "metrics_bench needs the GPU"
     dev = torch.device("cuda:0")
     rows = []
-    for H, W, nfix in SHAPES:
+    for H, W, nfix in (SHAPES if args.judd else ()):
         s1, f1 = _inputs(H, W, nfix, 1)
         t0 = time.perf_counter()
         M.auc_judd_rank(s1[0], f1[0])
@@ -117,6 +123,25 @@ def main():
             rows.append(dict(metric="IG", H=H, W=W, nfix=nfix, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32,
                              numpy_model_ms_per_map_one_core=host * 1e3))
             print(json.dumps(rows[-1]), flush=True)
+    if args.emd:
+        z = np.load(os.path.join(ROOT, "tests", "golden", "emd_fastemd.npz"))
+        ref = {(m["R"], m["C"]): m["cpu_seconds"] for m in json.loads(str(z["meta"])) if m["name"].startswith("dense_")}
+        for H, W in ((224, 384), (360, 640)):
+            R, C = -(-H // 32), -(-W // 32)
+            g8 = synth.saliency_maps("mbeg", 8, H, W, 3, noise=0.0)
+            p8 = synth.saliency_maps("mbep", 8, H, W, 4)
+            for B in (64, 256):
+                s, g = (torch.from_numpy(np.tile(a, (B // 8, 1, 1))).to(dev) for a in (p8, g8))
+                score, status, hist = loss.emd_batch(s, g, return_status=True, return_hist=True)
+                assert int(status.abs().sum()) == 0 and bool(torch.isfinite(score).all())
+                P, Q = hist[:, 0].contiguous(), hist[:, 1].contiguous()
+                reps = max(3, args.reps // 4)
+                t_all = _time(lambda: loss.emd_batch(s, g), reps)
+                t_solve = _time(lambda: loss.emd_hist_batch(P, Q, R, C), reps)
+                rows.append(dict(metric="EMD", H=H, W=W, bins="%dx%d" % (R, C), B=B, ms=t_all * 1e3, maps_per_s=B / t_all,
+                                 solver_only_ms=t_solve * 1e3, solver_only_maps_per_s=B / t_solve,
+                                 fastemd_cpu_ms_per_map_one_core=ref[(R, C)] * 1e3))
+                print(json.dumps(rows[-1]), flush=True)
     if args.forward:
         from vinet_amd import engine, model
         engine.set_default_dtype("bf16")

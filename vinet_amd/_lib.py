@@ -115,6 +115,10 @@ SIGNATURES = {
     "vinet_auc_borji_workspace": [_i32, _i32, _i32, _f64],
     "vinet_auc_borji": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _f64, _i64, _vp, _vp, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
     "vinet_info_gain": [_vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp],
+    "vinet_emd_workspace": [_i32, _i32, _i32],
+    "vinet_emd": [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp,
+                  _vp],
+    "vinet_emd_hist": [_vp, _vp, _i32, _i32, _i32, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
     "vinet_adam_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
     "vinet_bilinear_fwd": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "vinet_bilinear_bwd": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
@@ -140,6 +144,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"vinet_last_error": C.c_char_p, "vinet_conv3d_splitk_bytes": C.c_int64, "vinet_frames_preprocess_ws_bytes": C.c_int64,
             "vinet_gt_preprocess_ws_bytes": C.c_int64, "vinet_auc_judd_workspace": C.c_size_t, "vinet_auc_shuffled_workspace": C.c_size_t, "vinet_auc_borji_workspace": C.c_size_t,
+            "vinet_emd_workspace": C.c_size_t,
             "vinet_transformer_workspace": C.c_int64}
 
 _LIB = None

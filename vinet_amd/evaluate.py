@@ -4,6 +4,7 @@
     python -m vinet_amd.evaluate --pred_dir P --gt_dir G [--fix_dir F] [--batch 64] [--blur] [--json out.json]
                                  [--sauc [--other_map FILE] [--sauc_splits 100] [--sauc_step 0.1]]
                                  [--borji [--borji_splits 100] [--borji_step 0.1]] [--ig [--baseline FILE]]
+                                 [--emd [--emd_downsize 32]]
     python -m vinet_amd.evaluate --synthetic N          (N generated frames, no directory)
 
     P/<video>/<frame>.png|jpg            predicted maps
@@ -31,6 +32,12 @@ to the ground truth's size on the device) or, by default, leave-one-video-out: a
 maps on the device, and video v is scored against the total minus its own sum (with a single video: against the total, and
 the output says so).  That default needs ground-truth maps of one size.  NaN frames of either column are accounted for as
 the sAUC's are: `borji_skipped`, `ig_skipped`.
+
+`--emd` adds the earth mover's distance (code_for_Metrics/EMD.m, `loss.emd_batch`) as the column `EMD`, between the resized
+prediction and the ground-truth map: both are brought to ceil(H / d) x ceil(W / d) bins with MATLAB's imresize, d =
+`--emd_downsize` (32 as in EMD.m), divided by their sums, and FastEMD's transportation problem is solved exactly on the device.
+Lower is better.  A frame whose EMD alone is NaN (a map that sums to zero) is counted as `emd_skipped`, beside `emd_frames` and
+`emd_videos`, as the other optional columns are.
 """
 import argparse
 import json
@@ -42,7 +49,7 @@ import numpy as np
 import torch
 
 METRICS = ("SIM", "CC", "NSS", "AUCJ", "KLdiv")          # the order of diem_val.py:163-172, KLdiv appended
-EXTRA = (("sauc", "sAUC"), ("borji", "AUCB"), ("ig", "IG"))          # optional columns (flag, name), each with NaN counts of its own
+EXTRA = (("sauc", "sAUC"), ("borji", "AUCB"), ("ig", "IG"), ("emd", "EMD"))          # optional columns (flag, name), each with NaN counts of its own
 _IMG = (".png", ".jpg", ".jpeg")
 
 
@@ -114,12 +121,12 @@ def synthetic_videos(n):
     return videos
 
 
-def frame_metrics(pred_u8, gt_u8, fix_u8, blur=False, noise=None, sauc=None, borji=None, ig=None):
+def frame_metrics(pred_u8, gt_u8, fix_u8, blur=False, noise=None, sauc=None, borji=None, ig=None, emd=None):
     """uint8 device tensors [B,h,w], [B,H,W], [B,H,W] -> {metric: float64 [B] tensor}: diem_val.py:198-221 process() after the
     model call, for a batch.  `noise`: float64 [B,H,W] jitter for AUC-Judd (loss.py:160) or None.  `sauc`: None, or the
     keywords of loss.auc_shuffled_batch (other_map, frame_ids, n_splits, step, seed), which adds "sAUC".  `borji`: None, or the
     keywords of loss.auc_borji_batch (frame_ids, n_splits, step, seed), which adds "AUCB".  `ig`: None, or a dict with the
-    `baseline` of loss.info_gain_batch, which adds "IG"."""
+    `baseline` of loss.info_gain_batch, which adds "IG".  `emd`: None, or a dict with the `downsize` of loss.emd_batch, which adds "EMD"."""
     from . import loss, preprocess, utils
     size = tuple(gt_u8.shape[1:])
     if blur:
@@ -137,16 +144,18 @@ def frame_metrics(pred_u8, gt_u8, fix_u8, blur=False, noise=None, sauc=None, bor
         res["AUCB"] = loss.auc_borji_batch(s, fix, **borji)
     if ig is not None:
         res["IG"] = loss.info_gain_batch(s, fix, ig["baseline"])
+    if emd is not None:
+        res["EMD"] = loss.emd_batch(s, gt, downsize=emd["downsize"])
     return res
 
 
 class Scores:
     """the sums of diem_val.py:76-86 and :96-100; frames whose SIM, CC or NSS is NaN are skipped and counted.  `sauc=True`,
-    `borji=True` and `ig=True` keep the further columns "sAUC", "AUCB" and "IG", each with counts of its own: a scored frame
+    `borji=True`, `ig=True` and `emd=True` keep the further columns "sAUC", "AUCB", "IG" and "EMD", each with counts of its own: a scored frame
     whose value in such a column is NaN is left out of that column only."""
 
-    def __init__(self, sauc=False, borji=False, ig=False):
-        self.sauc, self.borji, self.ig = sauc, borji, ig
+    def __init__(self, sauc=False, borji=False, ig=False, emd=False):
+        self.sauc, self.borji, self.ig, self.emd = sauc, borji, ig, emd
         self.extra = tuple((flag, col) for flag, col in EXTRA if getattr(self, flag))
         self.cols = METRICS + tuple(col for _, col in self.extra)
         self.frame_sum = dict.fromkeys(METRICS, 0.0)
@@ -303,13 +312,14 @@ def video_gt_sums(videos, device, batch=64):
     return sums
 
 
-def evaluate(videos, device, batch=64, blur=False, jitter=True, per_frame=False, seed=0, sauc=None, borji=None, ig=None):
+def evaluate(videos, device, batch=64, blur=False, jitter=True, per_frame=False, seed=0, sauc=None, borji=None, ig=None, emd=None):
     """videos: collect()'s paths or synthetic_videos()'s arrays -> Scores.  `sauc`: None, or a dict with `n_splits`, `step` and
     `other_map` (uint8 [H,W] array for every video, or None for each video's own union).  `borji`: None, or a dict with
-    `n_splits` and `step`.  `ig`: None, or a dict with `baseline` (a [H,W] array for every video, or None for leave-one-video-out)"""
+    `n_splits` and `step`.  `ig`: None, or a dict with `baseline` (a [H,W] array for every video, or None for leave-one-video-out).
+    `emd`: None, or a dict with `downsize`"""
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
-    scores = Scores(sauc=sauc is not None, borji=borji is not None, ig=ig is not None)
+    scores = Scores(sauc=sauc is not None, borji=borji is not None, ig=ig is not None, emd=emd is not None)
     cols = scores.cols
     frame_no = 0          # the running frame number of the run: the frame id of the sAUC and AUC-Borji draws
     base_file = base_sums = base_total = None
@@ -356,6 +366,8 @@ def evaluate(videos, device, batch=64, blur=False, jitter=True, per_frame=False,
                         base_cache[size] = _baseline_for(base_file, size, device)
                     base_dev = base_cache[size]
                 more["ig"] = dict(baseline=base_dev)
+            if emd is not None:
+                more["emd"] = dict(downsize=emd["downsize"])
             res = frame_metrics(up(1), gt_u8, up(3), blur=blur, noise=noise, **more)
             frame_no += len(chunk)
             for m in cols:
@@ -383,6 +395,8 @@ def main(argv=None):
     p.add_argument('--borji_step', default=0.1, type=float, help="--borji: threshold step (AUC_Borji.m stepSize)")
     p.add_argument('--ig', action='store_true', help="add the information gain (InfoGain.m) as the column IG")
     p.add_argument('--baseline', default=None, type=str, help="--ig: one .npy / image baseline map for every video (default: leave-one-video-out sum of the ground truth)")
+    p.add_argument('--emd', action='store_true', help="add the earth mover's distance (EMD.m) as the column EMD")
+    p.add_argument('--emd_downsize', default=32, type=int, help="--emd: the maps are resized by 1 / this before the transport problem (EMD.m downsize)")
     p.add_argument('--per_frame', action='store_true', help="keep every frame's values in the JSON")
     p.add_argument('--json', default=None, type=str)
     p.add_argument('--synthetic', default=0, type=int, help="score N generated frames, no directory needed")
@@ -405,8 +419,9 @@ def main(argv=None):
         ig = dict(baseline=load_baseline(args.baseline) if args.baseline else None)
     elif args.baseline:
         p.error("--baseline needs --ig")
+    emd = dict(downsize=args.emd_downsize) if args.emd else None
     scores = evaluate(videos, torch.device(args.device), batch=args.batch, blur=args.blur, jitter=bool(args.jitter),
-                      per_frame=args.per_frame, seed=args.seed, sauc=sauc, borji=borji, ig=ig)
+                      per_frame=args.per_frame, seed=args.seed, sauc=sauc, borji=borji, ig=ig, emd=emd)
     s = scores.report()
     if args.json:
         with open(args.json, "w") as f:

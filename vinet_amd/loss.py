@@ -14,7 +14,9 @@ integer counts).  `auc_shuff` (loss.py:215-284) is left out on purpose: the refe
 reference's evaluation does compute is the MATLAB one (code_for_Metrics/AUC_shuffled.m, called from eval_diem.m): that is
 `auc_shuffled` / `auc_shuffled_batch` here (libvinet_hip.so: vinet_auc_shuffled), with `shuffle_map` for createShuffmap1.m.
 The two other fixation metrics of that folder run on the device as well: `auc_borji` / `auc_borji_batch` (AUC_Borji.m;
-vinet_auc_borji) and `info_gain` / `info_gain_batch` (InfoGain.m, IG.m; vinet_info_gain).
+vinet_auc_borji) and `info_gain` / `info_gain_batch` (InfoGain.m, IG.m; vinet_info_gain).  The distribution metric of that
+folder that is not a loss, the earth mover's distance, is `emd` / `emd_batch` (EMD.m; vinet_emd), with `emd_hist_batch` for
+histograms that are already downsampled (vinet_emd_hist).
 """
 import torch
 
@@ -358,6 +360,100 @@ def info_gain(saliencyMap, fixationMap, baselineMap=None):
     f = fixationMap[:1] if fixationMap.dim() == 3 else fixationMap.unsqueeze(0)
     bl = None if baselineMap is None else (baselineMap[0] if baselineMap.dim() == 3 else baselineMap)
     return float(info_gain_batch(s, f, bl)[0])
+
+
+_EMD_WEIGHTS = {}
+
+
+def _emd_weights(n_in, n_out, scale, device):
+    """utils.matlab_resize_weights on `device`, uploaded once per (n_in, n_out, scale, device)"""
+    key = (n_in, n_out, float(scale), str(device))
+    if key not in _EMD_WEIGHTS:
+        from . import utils
+        _EMD_WEIGHTS[key] = utils.matlab_resize_weights(n_in, n_out, float(scale)).to(device).contiguous()
+    return _EMD_WEIGHTS[key]
+
+
+def _emd_outputs(B, dev, return_cost, return_status):
+    score = torch.empty(B, dtype=torch.float64, device=dev)
+    cost = torch.empty(B, dtype=torch.int64, device=dev) if return_cost else None
+    status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
+    return score, cost, status
+
+
+def _emd_result(score, cost, status, more=()):
+    out = (score,) + tuple(x for x in (cost, status) if x is not None) + tuple(more)
+    return out[0] if len(out) == 1 else out
+
+
+@torch.no_grad()
+def emd_batch(s_maps, gt_maps, *, downsize=32, return_cost=False, return_status=False, return_hist=False):
+    """Earth mover's distance (EMD.m) of every pair of a batch: `[B,Hs,Ws]` saliency maps and `[B,Hg,Wg]` ground-truth maps,
+    float32 or float64, of any two sizes -> float64 `[B]` on the device.  The ground truth is resized by 1 / `downsize` to
+    R x C = ceil(Hg / downsize) x ceil(Wg / downsize) bins and the saliency map to that size (MATLAB's imresize: bicubic,
+    antialiased), each is divided by its sum, and FastEMD's emd_hat_gd_metric with the bins' Euclidean distance and no penalty
+    for extra mass is solved exactly on integers (1e6 units of mass, 1e6 steps of distance).  NaN where a resized map sums to
+    zero or holds a NaN, or the grid has a single bin.  At most 512 bins.
+    `return_cost`: also the integer optimum K `[B]` (int64); `return_status`: also the solver's status `[B]` (int32, 0 = solved;
+    include/vinet_hip.h); `return_hist`: also the two histograms, float64 `[B, 2, R*C]` (ground truth, saliency map)."""
+    assert s_maps.dim() == 3 and gt_maps.dim() == 3 and s_maps.shape[0] == gt_maps.shape[0], "expected [B,Hs,Ws] and [B,Hg,Wg] maps"
+    s = s_maps.detach()
+    if s.dtype not in (torch.float32, torch.float64):
+        s = s.float()
+    s = s.contiguous()
+    g = _fix_maps(gt_maps)
+    if g.device != s.device:
+        raise ValueError("emd: gt_maps on %s, the maps on %s" % (g.device, s.device))
+    dev = s.device
+    downsize = int(downsize)
+    B, (Hs, Ws), (Hg, Wg) = s.shape[0], s.shape[1:], g.shape[1:]
+    R, C = (-(-Hg // downsize), -(-Wg // downsize)) if downsize >= 1 else (0, 0)
+    lib = L.get()
+    need = int(lib.vinet_emd_workspace(B, R, C))
+    wts = [None] * 4
+    if need:          # (else the library refuses the call below and says why)
+        wts = [_emd_weights(Hg, R, 1.0 / downsize, dev), _emd_weights(Wg, C, 1.0 / downsize, dev),
+               _emd_weights(Hs, R, R / Hs, dev), _emd_weights(Ws, C, C / Ws, dev)]
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    score, cost, status = _emd_outputs(B, dev, return_cost, return_status)
+    hist = torch.empty((B, 2, R * C), dtype=torch.float64, device=dev) if return_hist else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    L.check(lib.vinet_emd(s.data_ptr(), 1 if s.dtype == torch.float64 else 0, Hs, Ws, g.data_ptr(), 1 if g.dtype == torch.float64 else 0,
+                          Hg, Wg, B, downsize, R, C, ptr(wts[0]), ptr(wts[1]), ptr(wts[2]), ptr(wts[3]), ws.data_ptr(), need, score.data_ptr(),
+                          ptr(cost), ptr(status), ptr(hist), E._stream_for(dev)), "vinet_emd")
+    return _emd_result(score, cost, status, (hist,) if return_hist else ())
+
+
+@torch.no_grad()
+def emd_hist_batch(P, Q, R, C, *, return_cost=False, return_status=False):
+    """The solver of `emd_batch` on ready histograms: `P`, `Q` `[B, R*C]` (or `[B,R,C]`), float32 or float64, the bins of an
+    R x C grid in row-major order -> float64 `[B]` on the device.  The histograms are taken as they are (FastEMD scales by
+    max(sum P, sum Q) itself); negative bins are allowed."""
+    R, C = int(R), int(C)
+    assert P.shape == Q.shape and P.dim() in (2, 3) and P[0].numel() == R * C, "expected P and Q as [B, R*C]"
+    if P.device != Q.device:
+        raise ValueError("emd_hist: P on %s, Q on %s" % (P.device, Q.device))
+    p, q = (x.detach().double().contiguous() for x in (P, Q))
+    B, dev = p.shape[0], p.device
+    lib = L.get()
+    need = int(lib.vinet_emd_workspace(B, R, C))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    score, cost, status = _emd_outputs(B, dev, return_cost, return_status)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    L.check(lib.vinet_emd_hist(p.data_ptr(), q.data_ptr(), B, R, C, ws.data_ptr(), need, score.data_ptr(), ptr(cost), ptr(status),
+                               E._stream_for(dev)), "vinet_emd_hist")
+    return _emd_result(score, cost, status)
+
+
+def emd(saliencyMap, fixationMap, toPlot=False, downsize=32):
+    """EMD.m's signature: a 2-D saliency map and a 2-D ground-truth map of any two sizes (or item 0 of 3-D batches, as `auc_judd`
+    takes them) -> Python float."""
+    if toPlot:
+        raise NotImplementedError("emd(toPlot=True) draws with matplotlib on the host; plot the returned score's inputs yourself")
+    assert saliencyMap.dim() in (2, 3) and fixationMap.dim() in (2, 3), "expected [H,W] maps or [B,H,W] batches"
+    s = saliencyMap[:1] if saliencyMap.dim() == 3 else saliencyMap.unsqueeze(0)
+    f = fixationMap[:1] if fixationMap.dim() == 3 else fixationMap.unsqueeze(0)
+    return float(emd_batch(s, f, downsize=downsize)[0])
 
 
 @torch.no_grad()

@@ -345,6 +345,19 @@ def _(s_maps, fix_maps, baseline):
     return s_maps.new_empty((s_maps.shape[0],), dtype=torch.float64)
 
 
+# ---- earth mover's distance (validation metric: no autograd) ---------------------------------------------------------------------------
+@torch.library.custom_op("vinet::emd", mutates_args=())
+def emd(s_maps: Tensor, gt_maps: Tensor, downsize: int) -> Tensor:
+    """[B,Hs,Ws] saliency maps and [B,Hg,Wg] ground-truth maps (EMD.m) -> fp64 [B] scores, NaN allowed"""
+    from . import loss as VL
+    return VL.emd_batch(s_maps, gt_maps, downsize=downsize)
+
+
+@emd.register_fake
+def _(s_maps, gt_maps, downsize):
+    return s_maps.new_empty((s_maps.shape[0],), dtype=torch.float64)
+
+
 # ---- fused Adam over a flat buffer ----------------------------------------------------------------------------------------------
 @torch.library.custom_op("vinet::adam_step_", mutates_args=("p", "m", "v"))
 def adam_step_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: float, beta2: float, eps: float, step: int, grad_scale: float) -> None:

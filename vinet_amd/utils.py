@@ -5,6 +5,8 @@ cv2.resize + cv2.GaussianBlur + the make_grid normalisation + uint8 conversion r
 (libvinet_hip.so: vinet_resize_blur, vinet_minmax, vinet_normalize_u8), so a predicted map leaves the GPU once, as
 bytes.  `resize_blur` and `to_uint8` are the fused forms the harness uses.
 """
+import functools
+
 import torch
 
 from . import _lib as L
@@ -98,6 +100,39 @@ def resize_blur(smap, size=None, return_minmax=False):
                                       E._stream_for(m.device)), "vinet_resize_blur")
     out = out[0] if smap.dim() == 2 else out
     return (out, mm) if return_minmax else out
+
+
+def _cubic(t):
+    a = abs(t)
+    if a <= 1.0:
+        return 1.5 * a ** 3 - 2.5 * a ** 2 + 1.0
+    if a <= 2.0:
+        return -0.5 * a ** 3 + 2.5 * a ** 2 - 4.0 * a + 2.0
+    return 0.0
+
+
+@functools.lru_cache(maxsize=64)
+def matlab_resize_weights(n_in, n_out, scale):
+    """MATLAB's default imresize (bicubic, antialiased when shrinking) along one dimension as a dense float64 [n_out, n_in] host
+    tensor: imresize's `contributions`.  Output x = 1 .. n_out sits at u = x / s + 0.5 (1 - 1 / s); the kernel is
+    h(t) = s cubic(s t) of width 4 / s for s < 1 and cubic of width 4 otherwise; the taps are floor(u - width / 2) and the
+    ceil(width) + 1 indices after it; their weights are normalised to sum 1; indices are clamped into [1, n_in] and the weights of
+    clamped taps add up.  Built once per (n_in, n_out, scale); `loss.emd_batch` (EMD.m:33-34) is its user."""
+    import math
+    s = float(scale)
+    width = 4.0 / s if s < 1.0 else 4.0
+    W = torch.zeros((n_out, n_in), dtype=torch.float64)
+    for x in range(1, n_out + 1):
+        u = x / s + 0.5 * (1.0 - 1.0 / s)
+        left = int(math.floor(u - width / 2.0))
+        idx = [left + k for k in range(int(math.ceil(width)) + 2)]
+        w = [s * _cubic(s * (u - i)) for i in idx] if s < 1.0 else [_cubic(u - i) for i in idx]
+        tot = 0.0
+        for v in w:
+            tot += v
+        for i, v in zip(idx, w):
+            W[x - 1, min(max(i, 1), n_in) - 1] += v / tot
+    return W
 
 
 def blur(img):
