@@ -1,5 +1,5 @@
 """AUC-Borji (code_for_Metrics/AUC_Borji.m) and the information gain (InfoGain.m, IG.m) in numpy, float64: the statements the HIP
-kernels (vinet_amd/csrc/metrics.hip: borji_split_kernel, info_gain_kernel) implement, and the models the CPU tests put in their
+kernels (vinet_amd/csrc/metrics.hip: split_auc_kernel with BorjiDraw, info_gain_kernel) implement, and the models the CPU tests put in their
 place.
 
 AUC-Borji, per map S (float32 or float64) and fixation map F:

@@ -1,4 +1,4 @@
-"""AUC-Borji and the information gain on the device (vinet_amd/csrc/metrics.hip: borji_split_kernel, info_gain_kernel) against
+"""AUC-Borji and the information gain on the device (vinet_amd/csrc/metrics.hip: split_auc_kernel with BorjiDraw, info_gain_kernel) against
 their numpy statements (tests/borji_ig_model.py).
 
 Bounds.  AUC-Borji: `nfix` and every count are integers: exact.  tp and fp are quotients of exact integers and every term of a

@@ -91,6 +91,38 @@ def test_python_surface_has_no_cpu_fallback():
     assert not hasattr(loss, "auc_shuff")
 
 
+def test_companion_tensor_on_another_device_is_refused_before_the_library(monkeypatch):
+    """Maps on the meta device, one companion tensor on the CPU: every metric raises a ValueError that names itself and the argument,
+    and none of them reaches the library on the way (a host pointer handed to a kernel is a device fault, not a Python error)."""
+    import torch
+    from vinet_amd import loss
+
+    def reached():
+        raise AssertionError("the library was reached")
+
+    monkeypatch.setattr(L, "get", reached)
+    meta = torch.device("meta")
+    s, cpu = torch.empty(2, 8, 8, device=meta), torch.ones(2, 8, 8)
+    hist, hist_cpu = torch.empty(2, 6, device=meta), torch.ones(2, 6)
+    with pytest.raises(AssertionError, match="the library was reached"):          # (with everything in one place the call goes on)
+        loss.auc_judd_batch(s, s)
+    for metric, arg, call in (
+            ("auc_judd", "fix_maps", lambda: loss.auc_judd_batch(s, cpu)),
+            ("auc_judd", "noise", lambda: loss.auc_judd_batch(s, s, noise=cpu.double())),
+            ("auc_shuffled", "fix_maps", lambda: loss.auc_shuffled_batch(s, cpu, s[0])),
+            ("auc_shuffled", "other_map", lambda: loss.auc_shuffled_batch(s, s, cpu[0])),
+            ("auc_borji", "fix_maps", lambda: loss.auc_borji_batch(s, cpu)),
+            ("info_gain", "fix_maps", lambda: loss.info_gain_batch(s, cpu)),
+            ("info_gain", "baseline", lambda: loss.info_gain_batch(s, s, cpu[0])),
+            ("emd", "gt_maps", lambda: loss.emd_batch(s, cpu)),
+            ("emd_hist", "Q", lambda: loss.emd_hist_batch(hist, hist_cpu, 2, 3)),
+            ("nss", "gt", lambda: loss.nss(s, cpu)),
+            ("per_sample", "gt", lambda: loss.per_sample("cc", s, cpu)),
+            ("kldiv", "gt", lambda: loss.kldiv(s, cpu))):
+        with pytest.raises(ValueError, match=r"^%s: %s on cpu, the maps on meta$" % (metric, arg)):
+            call()
+
+
 # ---- the evaluator on a tiny tree, metric functions replaced by numpy ------------------------------------------------------------
 def _model_metrics(pred_u8, gt_u8, fix_u8, blur=False, noise=None):
     """numpy stand-in for evaluate.frame_metrics on equal-size maps: SIM / CC / NSS / KLdiv by their definitions (loss.py), AUC-J by

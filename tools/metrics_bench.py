@@ -2,7 +2,7 @@
 """maps/s of vinet_amd.loss.auc_judd_batch, auc_shuffled_batch, auc_borji_batch and info_gain_batch on the device, beside their
 numpy models (tests/auc_model.py, tests/sauc_model.py, tests/borji_ig_model.py) on the host.
 
-    python tools/metrics_bench.py [--reps 20] [--json out.json] [--forward 1]
+    python tools/metrics_bench.py [--reps 20] [--json out.json] [--forward 1] [--dump out.npz]
 
 Shapes: 224x384 / 60 fixations, 360x640 / 900, 1080x1920 / 20 000 (above the kernel's LDS switch point: workspace route),
 each at B = 1 and 64.  s-AUC rows (`--sauc 0` leaves them out): the same shapes with an other set of 600 / 20 000 / 100 000
@@ -14,7 +14,9 @@ should stay below.  EMD rows (`--emd 0` leaves them out): `loss.emd_batch` end t
 at 7x12 bins (224x384 maps) and 12x20 bins (360x640) at downsize 32, B = 64 and 256, eight different map pairs repeated over the
 batch; the host column is not a model but the CPU time of the reference's own solver on a dense histogram of that grid, as
 tests/golden/make_emd_goldens.py recorded it (one core).  `--judd 0` leaves the AUC-Judd rows out.  No GPU: the device columns
-fail, nothing falls back.
+fail, nothing falls back.  `--dump FILE.npz` also stores what every row computed, for comparing two builds of the library bit for
+bit (VINET_LIB selects one): per row, under "<row>/<name>", the scores of the calls it timed and, for the two drawn metrics, the
+samples of one `return_samples` call; the jitter noise is seeded then.
 """
 import argparse
 import json
@@ -53,6 +55,12 @@ def _time(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def _keep(dump, row, **results):
+    """device results of one row -> dump["<row>/<name>"] (numpy); `row` from the row's own fields"""
+    key = "_".join(str(row[k]) for k in ("metric", "H", "W", "B"))
+    dump.update({"%s/%s" % (key, name): r.cpu().numpy() for name, r in results.items()})
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", default=20, type=int)
@@ -63,10 +71,15 @@ def main():
     p.add_argument("--ig", default=1, type=int)
     p.add_argument("--emd", default=1, type=int)
     p.add_argument("--judd", default=1, type=int)
+    p.add_argument("--dump", default=None, help="FILE.npz: the device results of every row")
     args = p.parse_args()
     assert torch.cuda.is_available(), "metrics_bench needs the GPU"
     dev = torch.device("cuda:0")
     rows = []
+    dump = None
+    if args.dump:
+        dump = {}
+        torch.manual_seed(0)
     for H, W, nfix in (SHAPES if args.judd else ()):
         s1, f1 = _inputs(H, W, nfix, 1)
         t0 = time.perf_counter()
@@ -81,6 +94,8 @@ def main():
             rows.append(dict(H=H, W=W, nfix=nfix, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32, ms_jitter_fp64=t64 * 1e3,
                              maps_per_s_jitter_fp64=B / t64, numpy_model_ms_per_map_one_core=host * 1e3))
             print(json.dumps(rows[-1]), flush=True)
+            if dump is not None:
+                _keep(dump, dict(rows[-1], metric="AUCJ"), fp32=loss.auc_judd_batch(s, f), jitter_fp64=loss.auc_judd_batch(s, f, noise=noise))
     for (H, W, nfix), nother in zip(SHAPES, SAUC_OTHERS if args.sauc else ()):
         s1, f1 = _inputs(H, W, nfix, 1)
         so = synth.saliency_maps("mbo", 1, H, W, 12)
@@ -97,6 +112,8 @@ def main():
             rows.append(dict(metric="sAUC", H=H, W=W, nfix=nfix, nother=int(oth.size), splits=100, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32,
                              numpy_model_ms_per_map_one_core=host * 1e3))
             print(json.dumps(rows[-1]), flush=True)
+            if dump is not None:
+                _keep(dump, rows[-1], score=loss.auc_shuffled_batch(s, f, o), samples=loss.auc_shuffled_batch(s, f, o, return_samples=True)[3])
     for H, W, nfix in (SHAPES if args.borji else ()):
         s1, f1 = _inputs(H, W, nfix, 1)
         t0 = time.perf_counter()
@@ -109,6 +126,8 @@ def main():
             rows.append(dict(metric="AUCB", H=H, W=W, nfix=nfix, splits=100, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32,
                              numpy_model_ms_per_map_one_core=host * 1e3))
             print(json.dumps(rows[-1]), flush=True)
+            if dump is not None:
+                _keep(dump, rows[-1], score=loss.auc_borji_batch(s, f), samples=loss.auc_borji_batch(s, f, return_samples=True)[2])
     for H, W, nfix in (SHAPES if args.ig else ()):
         s1, f1 = _inputs(H, W, nfix, 1)
         b1 = synth.saliency_maps("mbb", 1, H, W, 9, noise=0.0)[0]
@@ -123,6 +142,8 @@ def main():
             rows.append(dict(metric="IG", H=H, W=W, nfix=nfix, B=B, ms_fp32=t32 * 1e3, maps_per_s_fp32=B / t32,
                              numpy_model_ms_per_map_one_core=host * 1e3))
             print(json.dumps(rows[-1]), flush=True)
+            if dump is not None:
+                _keep(dump, rows[-1], score=loss.info_gain_batch(s, f, base))
     if args.emd:
         z = np.load(os.path.join(ROOT, "tests", "golden", "emd_fastemd.npz"))
         ref = {(m["R"], m["C"]): m["cpu_seconds"] for m in json.loads(str(z["meta"])) if m["name"].startswith("dense_")}
@@ -142,6 +163,8 @@ def main():
                                  solver_only_ms=t_solve * 1e3, solver_only_maps_per_s=B / t_solve,
                                  fastemd_cpu_ms_per_map_one_core=ref[(R, C)] * 1e3))
                 print(json.dumps(rows[-1]), flush=True)
+                if dump is not None:
+                    _keep(dump, rows[-1], score=loss.emd_batch(s, g), solver_only=loss.emd_hist_batch(P, Q, R, C))
     if args.forward:
         from vinet_amd import engine, model
         engine.set_default_dtype("bf16")
@@ -156,6 +179,8 @@ def main():
     if args.json:
         with open(args.json, "w") as fh:
             json.dump(rows, fh, indent=1)
+    if dump is not None:
+        np.savez(args.dump, **dump)
 
 
 if __name__ == "__main__":

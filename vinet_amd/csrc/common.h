@@ -259,6 +259,8 @@ template <bool G64> VN_DEV double ldg(const void* gt, long i) {
   if (G64) return ((const double*)gt)[i];
   return (double)((const float*)gt)[i];
 }
+// the same where the dtype is a kernel argument (the fp64 metrics: info gain, EMD)
+VN_DEV double ldg_rt(const void* gt, int is64, long i) { return is64 ? ((const double*)gt)[i] : (double)((const float*)gt)[i]; }
 
 struct MinIdx { double v; int i; };
 
@@ -332,6 +334,8 @@ static inline int vn_wgrad_cus(const VinetWgradDesc* d) {
 // fp32 tensors in memory: the exact fp32-MFMA path and its split-bf16 arithmetic form (VINET_F32S)
 static inline bool vn_f32_storage(int dt) { return dt == VINET_F32 || dt == VINET_F32S; }
 static inline int vn_div_up(long a, long b) { return (int)((a + b - 1) / b); }
+// workspace sections start 8-byte aligned
+static inline size_t vn_pad8(size_t v) { return (v + 7) / 8 * 8; }
 // `overlap`: a read-only conv input may be an OVERLAPPED view (ld < C): consecutive W positions share
 // channels.  The folded RGB stem uses it (position = 2 pixels, "channels" = 8 pixels x 4).
 static inline bool vn_tensor_ok(const VinetTensor& t, int eg, bool overlap = false) {

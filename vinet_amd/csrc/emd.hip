@@ -64,9 +64,7 @@ struct EmdHead {
 };
 
 static size_t emd_flow_entries(int N) { return (size_t)(N / 2) * (size_t)((N + 1) / 2); }          // max S T with S + T <= N
-static size_t emd_ws_per_map(int N) { return sizeof(EmdHead) + 2 * (size_t)N * sizeof(long long) + (emd_flow_entries(N) * 4 + 7) / 8 * 8; }
-
-VN_DEV double emd_ld(const void* p, int is64, long i) { return is64 ? ((const double*)p)[i] : (double)((const float*)p)[i]; }
+static size_t emd_ws_per_map(int N) { return sizeof(EmdHead) + 2 * (size_t)N * sizeof(long long) + vn_pad8(emd_flow_entries(N) * 4); }
 
 VN_DEV long long emd_block_sum_ll(long long v, long long* sh) {
 #pragma unroll
@@ -131,7 +129,7 @@ VN_DEV void emd_resize(const void* x, int is64, int H, int W, const double* __re
 #pragma unroll
         for (int k = 0; k < EMD_TILE / EMD_LANES; ++k) {
           const int w = w0 + tid + k * EMD_LANES;
-          if (w < W) acc[k] += wt * emd_ld(x, is64, off + (long)h * W + w);
+          if (w < W) acc[k] += wt * ldg_rt(x, is64, off + (long)h * W + w);
         }
       }
       __syncthreads();          // the tile's readers of the pass before are done

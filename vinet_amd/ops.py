@@ -247,14 +247,8 @@ def upsample2x(x):
 @torch.library.custom_op("vinet::saliency_loss", mutates_args=())
 def saliency_loss(s_map: Tensor, gt: Tensor, which: int) -> Tuple[Tensor, Tensor]:
     """which: 0 kldiv, 1 cc, 2 similarity (loss.py:13-99) -> (loss scalar fp32, per-sample saved statistics)"""
-    s = s_map.float().contiguous()
-    g = gt.contiguous()
-    B, n = s.shape[0], s.shape[1] * s.shape[2]
-    saved = torch.empty(B * 8, dtype=torch.float64, device=s.device)
-    out = torch.empty((), dtype=torch.float32, device=s.device)
-    L.check(L.get().vinet_loss_fwd(which, s.data_ptr(), g.data_ptr(), 1 if g.dtype == torch.float64 else 0, B, n, saved.data_ptr(),
-                                   out.data_ptr(), E._stream_for(s.device)), "vinet_loss_fwd")
-    return out, saved
+    from . import loss as VL
+    return VL._loss_fwd(which, s_map.float().contiguous(), gt.contiguous())
 
 
 @saliency_loss.register_fake
