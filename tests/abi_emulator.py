@@ -690,6 +690,8 @@ class AbiEmulator:
         sv, gv = self._loss_inputs(s, gt, gt_is_f64, B, n)
         per = self._loss_value(which, sv, gv)
         _f32(loss, 1)[0] = float(per.mean())
+        # the per-sample value in its documented slot of saved[b][0..7] (csrc/loss_adam.hip; vinet_amd.loss.per_sample reads it)
+        np.ctypeslib.as_array((C.c_double * (B * 8)).from_address(saved)).reshape(B, 8)[:, 2 if which == 0 else 5] = per.numpy()
         return 0
 
     def vinet_loss_bwd(self, which, s, gt, gt_is_f64, B, n, saved, gscale, coeff, accumulate, ds, stream):
