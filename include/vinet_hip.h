@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define VINET_ABI_VERSION 16   /* still 16: vinet_emd, vinet_emd_hist and vinet_emd_workspace are pure additions as well; vinet_auc_borji, vinet_auc_borji_workspace and vinet_info_gain are pure additions (no existing entry point or struct changed); 16: vinet_auc_shuffled, vinet_auc_shuffled_workspace; 15: vinet_transformer_fwd / _bwd / _workspace; 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
+#define VINET_ABI_VERSION 16   /* still 16: vinet_token_encoder_fwd / _bwd / _workspace and vinet_token_split_fwd / _bwd are pure additions; vinet_emd, vinet_emd_hist and vinet_emd_workspace are pure additions as well; vinet_auc_borji, vinet_auc_borji_workspace and vinet_info_gain are pure additions (no existing entry point or struct changed); 16: vinet_auc_shuffled, vinet_auc_shuffled_workspace; 15: vinet_transformer_fwd / _bwd / _workspace; 14: vinet_auc_judd, vinet_auc_judd_workspace; 13 (round 6): tline 5 / 1 also promise weight slices < 64 */
 
 enum { VINET_F32 = 0, VINET_BF16 = 1,
        /* conv / weight-gradient descriptors only: fp32 tensors (as VINET_F32), bf16 matrix arithmetic on a two-term split of both
@@ -565,6 +565,39 @@ typedef struct VinetTransformerDesc {
 int64_t vinet_transformer_workspace(const VinetTransformerDesc* desc);
 int vinet_transformer_fwd(const VinetTransformerDesc* desc, const VinetTensor* x, const VinetTensor* y, void* stream);
 int vinet_transformer_bwd(const VinetTransformerDesc* desc, const VinetTensor* dy, const VinetTensor* dx, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Token-wise fusion (model.py:116-189, VideoAudioSaliencyFusionModel): the same PositionalEncoding + encoder stack, with the
+ * ROWS of the channels-last activation as tokens and its channels as features:  tokens[b][s][e] = x[b][position s][channel e]
+ * + pe[s][e].  x / y / dy / dx are views [B][T][H][W][C = E] with T*H*W = S, any ld >= C and any sB (position s of clip b at
+ * b sB + s ld); y may be a channel sub-view of a wider tensor, bytes outside the views are not touched.
+ * Arithmetic, parameter order, gradient accumulation, null gradients (grads[i] == NULL / dx == NULL are skipped), dropout
+ * (sites, stream 4 layer + site, device step counter) and the mask export layout are those of vinet_transformer_* above.
+ * Softmax rows are saved by forward; the workspace holds every clip's matrices on S rounded up to 16 rows.
+ * Limits: 1 <= S <= 1024, E % 16 == 0, E <= 512, F % 16 == 0, E % H == 0, E / H <= 128, (E / H) % 4 == 0, 0 <= p < 1.
+ * ---------------------------------------------------------------------- */
+typedef struct VinetTokenEncoderDesc {
+  int32_t dtype;
+  int32_t B, S, E, H, F, L;
+  int32_t train;
+  float p, eps;
+  uint64_t seed;
+  int64_t* step;
+  const float* pe;               /* [S][E] */
+  const void* const* params;
+  void* const* grads;
+  void* ws;
+  int64_t ws_bytes;
+  uint8_t* masks;
+} VinetTokenEncoderDesc;
+int64_t vinet_token_encoder_workspace(const VinetTokenEncoderDesc* desc);
+int vinet_token_encoder_fwd(const VinetTokenEncoderDesc* desc, const VinetTensor* x, const VinetTensor* y, void* stream);
+int vinet_token_encoder_bwd(const VinetTokenEncoderDesc* desc, const VinetTensor* dy, const VinetTensor* dx, void* stream);
+/* split / mean / broadcast behind it (model.py:175-185).  x = tokens [B][Sv + n_audio][E], y [B][Sv positions][2E]:
+ * y[b][pos][0:E] = x[b][pos], y[b][pos][E:2E] = mean over the n_audio last rows of x[b].  Backward writes (does not add)
+ * dx: rows [0, Sv) = dy[..., 0:E]; each audio row = (1 / n_audio) * the sum of dy[..., E:2E] over positions in index order. */
+int vinet_token_split_fwd(const VinetTensor* x, int32_t dtype, int32_t n_audio, const VinetTensor* y, void* stream);
+int vinet_token_split_bwd(const VinetTensor* dy, int32_t dtype, int32_t n_audio, const VinetTensor* dx, void* stream);
 
 /* ------------------------------------------------------------------------
  * Saliency-map post-processing: the host-side cv2 / torchvision steps of

@@ -3,11 +3,15 @@
 
   encoder   the fused HIP encoder stack (3 layers, 32 tokens x 336 features) forward and forward + backward at B = 1, 8, 32, 192
             against torch's own nn.TransformerEncoder in eager mode on the same device, weights and input (dropout 0 on both)
+  tokens    the token-wise encoder of VideoAudioSaliencyFusionModel (3 layers, 339 tokens x 512 features, 4 heads) forward and
+            forward + backward at --token_batches (default 1, 8, 32, 192) against eager nn.TransformerEncoder in fp32 on the same
+            device, weights and input (dropout 0 on both), the two alternating inside each timed round; with the achieved share of
+            the 155 TF/s fp32-MFMA rate (FLOPs counted from the shapes) and the workspace bytes per clip
   step      the AViNet training step (kldiv + fused Adam, --dtype) with and without use_transformer at --step_batches (default 1, 8, 32, 192)
 
 Warm-up, then the median of --repeats timed runs (device events around one call).  One JSON line per measurement on stdout.
 
-    python tools/transformer_bench.py [--what encoder,step] [--repeats 30] [--encoder_batches 1,8,32,192] [--step_batches 1,8,32,192] [--dtype bf16]
+    python tools/transformer_bench.py [--what encoder,tokens,step] [--repeats 30] [--encoder_batches 1,8,32,192] [--step_batches 1,8,32,192] [--dtype bf16]
 """
 import argparse
 import json
@@ -86,6 +90,93 @@ def bench_encoder(args, dev):
         print(json.dumps(row), flush=True)
 
 
+FP32_MFMA_PEAK = 155e12      # dense fp32-input MFMA rate of the MI355X, FLOP/s
+
+
+def token_layer_flops(S, Ef, F):
+    """forward FLOPs of one clip and layer: QKV, the two attention products, the out-projection, the two linears"""
+    return 2 * S * Ef * 3 * Ef + 2 * 2 * S * S * Ef + 2 * S * Ef * Ef + 2 * 2 * S * Ef * F
+
+
+def alternating_ms(fns, warmup, repeats):
+    """median and minimum ms of each callable, the callables taking turns inside every round (other people's work shares the host:
+    a drift then falls on all of them alike)"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts[k].append(e0.elapsed_time(e1))
+    return {k: (statistics.median(v), min(v)) for k, v in ts.items()}
+
+
+def bench_tokens(args, dev):
+    import ctypes as C
+    from vinet_amd import _lib as L
+    from vinet_amd import model as VM
+    E.set_default_dtype("fp32")
+    S, Ef, H, NL = 339, 512, 4, 3
+    tf = VM._TransformerParams(Ef, hidden_size=Ef, nhead=H, num_encoder_layers=NL, max_len=S, max_head_width=VM.TOKEN_ENCODER_MAX_HEAD_WIDTH)
+    sd = synth.synth_state_dict(tf.state_dict(), 1)
+    sd["pos_encoder.pe"] = tf.state_dict()["pos_encoder.pe"]
+    tf.load_state_dict(sd)
+    for l in tf.transformer_encoder.layers:
+        l.dropout.p = l.dropout1.p = l.dropout2.p = 0.0
+        l.self_attn.dropout = 0.0
+    tf = tf.to(dev).train()
+    aten = torch.nn.TransformerEncoder(torch.nn.TransformerEncoderLayer(Ef, H, Ef, dropout=0.0), NL, enable_nested_tensor=False).to(dev).train()
+    aten.load_state_dict({k[len("transformer_encoder."):]: v for k, v in sd.items() if k.startswith("transformer_encoder.")})
+    pe = sd["pos_encoder.pe"].to(dev)
+    flops = NL * token_layer_flops(S, Ef, Ef)
+    for B in [int(b) for b in args.token_batches.split(",")]:
+        x = synth.normal("bench_tok_x", (B, Ef, S, 1, 1), 2).to(dev)          # NCDHW: position = token, channel = feature
+        g = synth.normal("bench_tok_g", (B, Ef, S, 1, 1), 3).to(dev)
+        xt = x.reshape(B, Ef, S).permute(2, 0, 1).contiguous()                  # [S, B, E] for nn.TransformerEncoder
+        gt = g.reshape(B, Ef, S).permute(2, 0, 1).contiguous()
+
+        def hip_fwd():
+            with torch.no_grad():
+                return fusion.token_encoder_tokens(tf, x)
+
+        def hip_fb():
+            xr = x.detach().requires_grad_(True)
+            (fusion.token_encoder_tokens(tf, xr) * g).sum().backward()
+
+        def aten_fwd():
+            with torch.no_grad():
+                return aten(xt + pe)
+
+        def aten_fb():
+            xr = xt.detach().requires_grad_(True)
+            (aten(xr + pe) * gt).sum().backward()
+
+        with torch.no_grad():
+            diff = float((fusion.token_encoder_tokens(tf, x).reshape(B, Ef, S).permute(2, 0, 1) - aten(xt + pe)).abs().max())
+        reps = max(5, args.repeats // (1 if B <= 32 else 3))
+        row = dict(bench="token_encoder", B=B, S=S, E=Ef, H=H, L=NL, max_abs_diff_to_aten=diff, repeats=reps)
+        t = alternating_ms(dict(hip_fwd=hip_fwd, aten_fwd=aten_fwd), args.warmup, reps)
+        t.update(alternating_ms(dict(hip_fwd_bwd=hip_fb, aten_fwd_bwd=aten_fb), args.warmup, reps))
+        for name, (med, lo) in t.items():
+            row[name + "_ms"] = round(med, 4)
+            row[name + "_min_ms"] = round(lo, 4)
+        row["aten_over_hip_fwd"] = round(row["aten_fwd_ms"] / row["hip_fwd_ms"], 3)
+        row["aten_over_hip_fwd_bwd"] = round(row["aten_fwd_bwd_ms"] / row["hip_fwd_bwd_ms"], 3)
+        # whole-call rates (import / export of the NCDHW boundary and the host's launches included), not a kernel's share of peak
+        row["hip_fwd_share_of_fp32_mfma_peak"] = round(B * flops / (row["hip_fwd_ms"] * 1e-3) / FP32_MFMA_PEAK, 4)
+        row["hip_fwd_bwd_share_of_fp32_mfma_peak"] = round(3 * B * flops / (row["hip_fwd_bwd_ms"] * 1e-3) / FP32_MFMA_PEAK, 4)
+        d = L.CTokenEncoderDesc()
+        d.dtype, d.B, d.S, d.E, d.H, d.F, d.L, d.train, d.p, d.eps = L.F32, B, S, Ef, H, Ef, NL, 1, 0.0, 1e-5
+        row["workspace_bytes_per_clip"] = int(L.load().vinet_token_encoder_workspace(C.byref(d))) // B
+        print(json.dumps(row), flush=True)
+
+
 def bench_step(args, dev):
     from vinet_amd import loss as VL
     from vinet_amd import model as VM
@@ -137,11 +228,14 @@ def main():
     p.add_argument("--step_repeats", default=9, type=int)
     p.add_argument("--step_batches", default="1,8,32,192")
     p.add_argument("--encoder_batches", default="1,8,32,192")
+    p.add_argument("--token_batches", default="1,8,32,192")
     p.add_argument("--dtype", default="bf16")
     args = p.parse_args()
     dev = torch.device("cuda:0")
     if "encoder" in args.what:
         bench_encoder(args, dev)
+    if "tokens" in args.what:
+        bench_tokens(args, dev)
     if "step" in args.what:
         bench_step(args, dev)
 

@@ -63,9 +63,15 @@ class CTransformerDesc(C.Structure):
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("masks", C.c_void_p)]
 
 
+class CTokenEncoderDesc(C.Structure):
+    """VinetTokenEncoderDesc: the same fields as the channel-token encoder's descriptor"""
+    _fields_ = list(CTransformerDesc._fields_)
+
+
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 _PT, _PC, _PW, _PP = C.POINTER(CTensor), C.POINTER(CConvDesc), C.POINTER(CWgradDesc), C.POINTER(CPoolDesc)
 _PX = C.POINTER(CTransformerDesc)
+_PK = C.POINTER(CTokenEncoderDesc)
 
 # name -> argtypes (restype is always int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -125,6 +131,11 @@ SIGNATURES = {
     "vinet_transformer_workspace": [_PX],
     "vinet_transformer_fwd": [_PX, _PT, _PT, _vp],
     "vinet_transformer_bwd": [_PX, _PT, _PT, _vp],
+    "vinet_token_encoder_workspace": [_PK],
+    "vinet_token_encoder_fwd": [_PK, _PT, _PT, _vp],
+    "vinet_token_encoder_bwd": [_PK, _PT, _PT, _vp],
+    "vinet_token_split_fwd": [_PT, _i32, _i32, _PT, _vp],
+    "vinet_token_split_bwd": [_PT, _i32, _i32, _PT, _vp],
     "vinet_resize_blur": [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp],
     "vinet_minmax": [_vp, _i32, _i64, _vp, _vp],
     "vinet_normalize_u8": [_vp, _vp, _i32, _i64, _vp, _vp],
@@ -145,7 +156,7 @@ SIGNATURES = {
 _RESTYPE = {"vinet_last_error": C.c_char_p, "vinet_conv3d_splitk_bytes": C.c_int64, "vinet_frames_preprocess_ws_bytes": C.c_int64,
             "vinet_gt_preprocess_ws_bytes": C.c_int64, "vinet_auc_judd_workspace": C.c_size_t, "vinet_auc_shuffled_workspace": C.c_size_t, "vinet_auc_borji_workspace": C.c_size_t,
             "vinet_emd_workspace": C.c_size_t,
-            "vinet_transformer_workspace": C.c_int64}
+            "vinet_transformer_workspace": C.c_int64, "vinet_token_encoder_workspace": C.c_int64}
 
 _LIB = None
 _TEST_DOUBLE = None

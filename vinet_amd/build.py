@@ -16,7 +16,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "obj")
 LIB = os.path.join(HERE, "libvinet_hip.so")
-SOURCES = ["conv_api.hip", "conv_bf16.hip", "conv_bnb.hip", "conv_f32.hip", "conv_wgrad.hip", "wgrad_dma.hip", "wgrad_pp.hip", "wgrad_ts.hip", "conv_ts.hip", "wgrad_hs.hip", "wgrad_rs.hip", "wgrad_tf.hip", "conv_hs.hip", "layout.hip", "bn.hip", "pool.hip", "resample.hip", "loss_adam.hip", "metrics.hip", "emd.hip", "postproc.hip", "preproc.hip", "transformer.hip"]
+SOURCES = ["conv_api.hip", "conv_bf16.hip", "conv_bnb.hip", "conv_f32.hip", "conv_wgrad.hip", "wgrad_dma.hip", "wgrad_pp.hip", "wgrad_ts.hip", "conv_ts.hip", "wgrad_hs.hip", "wgrad_rs.hip", "wgrad_tf.hip", "conv_hs.hip", "layout.hip", "bn.hip", "pool.hip", "resample.hip", "loss_adam.hip", "metrics.hip", "emd.hip", "postproc.hip", "preproc.hip", "transformer.hip", "token_encoder.hip"]
 import glob
 # every header of csrc/ and include/ is a dependency of every object (a stale object travelling to the GPU box is worse
 # than a rebuild of 20 files)

@@ -294,7 +294,7 @@ class View:
 class Act:
     """activation = view + pending affine/relu + gradient bookkeeping."""
     __slots__ = ("v", "scale", "shift", "relu", "_grad", "grad_ready", "needs_grad", "parent", "pc0", "pt0", "fold",
-                 "indep", "ready_of", "grad_marks", "mean", "invstd", "alias_of", "n_readers", "act_out", "grad_masked")
+                 "indep", "ready_of", "grad_marks", "mean", "invstd", "alias_of", "n_readers", "act_out", "grad_masked", "prows")
 
     def __init__(self, v, scale=None, shift=None, relu=False, needs_grad=False, mean=None, invstd=None):
         self.v, self.scale, self.shift, self.relu = v, scale, shift, relu
@@ -311,6 +311,7 @@ class Act:
         self.n_readers = 0       # consumers recorded in this forward that will write this gradient (counted on the root)
         self.act_out = 0         # activation the producing conv applied in its epilogue (no BatchNorm): conv_forward
         self.grad_masked = -1    # grad_marks at which the gradient already carries that activation's backward (upsample2x backward)
+        self.prows = None        # (first row, T, H, W): a row range of the parent's positions under dims of its own (sub_rows)
 
     @property
     def plain(self):
@@ -340,6 +341,15 @@ class Act:
         a.parent, a.pt0, a.pc0 = self, t0, None
         return a
 
+    def sub_rows(self, r0, thw):
+        """`T H W` consecutive positions of a dense-row parent, from position r0, seen as [B, T, H, W, C] (the token matrix of the
+        token-wise fusion: one producer per row range).  Gradient storage and the gradient-ready flag are the parent's."""
+        v, (t, h, w) = self.v, thw
+        assert self.plain and v.sB >= v.T * v.H * v.W * v.ld and 0 <= r0 and r0 + t * h * w <= v.T * v.H * v.W
+        a = Act(View(v.buf, v.off + r0 * v.ld, v.B, t, h, w, v.C, v.ld, v.sB, v.dt), needs_grad=self.needs_grad)
+        a.parent, a.pc0, a.pt0, a.prows = self, None, None, (r0, t, h, w)
+        return a
+
     def root(self):
         """owner of the gradient-ready flag"""
         a = self
@@ -357,6 +367,9 @@ class Act:
                     top = top.parent
                 assert top._grad is None, "zero-filled gradient requested for a region of live shared storage"
             g = self.parent.grad_view(dt, zero)
+            if self.prows is not None:
+                r0, t, h, w = self.prows
+                return View(g.buf, g.off + r0 * g.ld, g.B, t, h, w, g.C, g.ld, g.sB, g.dt)
             if self.pt0 is None:
                 return g.chan(self.pc0, self.pc0 + self.v.C)
             return g.tslice(self.pt0, self.pt0 + self.v.T)

@@ -181,6 +181,11 @@ def validate(args, model=None, device=None):
     return n_saved
 
 
+def _flag(v):
+    """a boolean option that reads "False" / "0" / "no" as False (type=bool, which the reference's flags use, reads any non-empty string as True)"""
+    return v if isinstance(v, bool) else str(v).lower() not in ("", "0", "false", "no")
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument('--file_weight', default="./saved_models/no_trans_upsampling_reduced.pt", type=str)
@@ -202,12 +207,22 @@ def build_parser():
     p.add_argument('--use_sound', default=False, type=bool)
     p.add_argument('--use_transformer', default=False, type=bool,
                    help="the audio-visual model's transformer fusion (needs --use_sound True and --transformer_in_channel 32)")
+    p.add_argument('--token_fusion', default=False, type=_flag,
+                   help="BUILD-DEFINED (the reference's drivers never build this class): run VideoAudioSaliencyFusionModel, the "
+                        "token-wise transformer fusion (model.py:116-189), on 32-frame clips")
     p.add_argument('--compute_dtype', default="fp32s", choices=["bf16", "fp32", "fp32s"],
                    help="arithmetic of the HIP path.  Default fp32s (split-bf16 products, fp32 tensors): INSIDE the reference contract -- maps within "
                         "1e-3 of the PyTorch-CPU path, exact argmax.  bf16 is the throughput mode (2.9x faster; maps within 2.5e-2, gradients of the "
                         "encoder noisy: DESIGN.md) and must be asked for; fp32 is the exact-fp32-MFMA path")
     p.add_argument('--batch', default=1, type=int)
     return p
+
+
+def build_token_fusion_model(args):
+    from . import model
+    return model.VideoAudioSaliencyFusionModel(transformer_in_channel=args.transformer_in_channel, nhead=args.nhead,
+                                               num_encoder_layers=args.num_encoder_layers, use_upsample=bool(args.decoder_upsample),
+                                               num_hier=args.num_hier, num_clips=args.clip_size)
 
 
 def main(argv=None):
@@ -219,7 +234,10 @@ def main(argv=None):
     engine.set_default_dtype(args.compute_dtype)
     kw = dict(transformer_in_channel=args.transformer_in_channel, nhead=args.nhead, use_upsample=bool(args.decoder_upsample),
               num_hier=args.num_hier, num_clips=args.clip_size)
-    if args.use_sound:
+    if args.token_fusion:
+        args.use_sound = True          # (the fusion model always reads the waveform)
+        m = build_token_fusion_model(args)
+    elif args.use_sound:
         m = model.VideoAudioSaliencyModel(use_transformer=args.use_transformer, num_encoder_layers=args.num_encoder_layers, **kw)
     else:
         m = model.VideoSaliencyModel(**kw)

@@ -11,6 +11,14 @@ captured region contains only the steady-state kernels.
 import torch
 
 
+def _refuse_uncapturable(model):
+    """a module may name, in `graph_capture_refusal`, the reason why it must not be captured into a hipGraph"""
+    for mod in model.modules():
+        why = getattr(mod, "graph_capture_refusal", None)
+        if why:
+            raise NotImplementedError("%s cannot be captured into a hipGraph: %s" % (type(mod).__name__, why))
+
+
 class GraphedInference:
     """y = GraphedInference(model, example_inputs)(inputs): replays a captured forward.
 
@@ -18,6 +26,7 @@ class GraphedInference:
     (re-create the wrapper after loading new weights)."""
 
     def __init__(self, model, *example_inputs, warmup=2):
+        _refuse_uncapturable(model)
         assert all(t.is_cuda for t in example_inputs), "graph capture needs GPU tensors"
         self.model = model.eval()
         self.static_in = [t.clone() for t in example_inputs]
@@ -59,6 +68,7 @@ class GraphedTrainStep:
     """
 
     def __init__(self, model, optimizer, loss_fn, inputs, gt, warmup=2, debug_dot=None, keep_graph=False, launch_log=False):
+        _refuse_uncapturable(model)
         self.capture = all(t.is_cuda for t in inputs) and gt.is_cuda
         if not self.capture:
             from . import _lib

@@ -360,6 +360,80 @@ class VideoAudioSaliencyModel(nn.Module):
         return E.run_root(body, [x, audio], list(self.parameters()))[0]
 
 
+class VideoAudioSaliencyFusionModel(nn.Module):
+    """model.py:116-189: token-wise audio-visual fusion.  conv_in_1x1 turns y0 into 4 x 7 x 12 = 336 position tokens of 512
+    features, audio_conv_1x1 the 3 SoundNet time steps into 3 more; one transformer encoder runs over the 339 tokens, and the
+    decoder reads [video tokens | mean audio token at every position] (1024 channels).  `maxpool` and `bilinear` exist in the
+    reference's checkpoint but its forward never uses them: `bilinear` keeps its parameters here and stays out of the optimizer.
+    The SoundNet checkpoint is handled as in VideoAudioSaliencyModel."""
+    compute_dtype = None
+    soundnet_checkpoint = "./soundnet8_final.pth"
+    unused_parameter_names = ("bilinear.weight", "bilinear.bias")
+    # graph.GraphedTrainStep / GraphedInference refuse this model: a captured step of it has never been replayed under test (every
+    # forward allocates the encoder's workspace inside the capture and advances the device step counter there), and the one
+    # process that captured it later crashed in the replay of another model's graph, cause unknown.  Lifted together with a
+    # graph-replay test of this model.
+    graph_capture_refusal = ("a captured step of the token-wise fusion model has never been replayed under test, and a process "
+                             "that captured one later crashed inside hipGraph replay (cause not found); run it eagerly")
+    N_VIDEO_TOKENS, N_AUDIO_TOKENS = 4 * 7 * 12, 3
+
+    def __init__(self, use_transformer=True, transformer_in_channel=512, num_encoder_layers=3, nhead=4,
+                 use_upsample=True, num_hier=3, num_clips=32):
+        super().__init__()
+        self.use_transformer = use_transformer           # (stored and ignored, as in the reference)
+        if transformer_in_channel != 512:
+            raise NotImplementedError("the fusion model needs transformer_in_channel=512: the decoder's first conv reads the video "
+                                      "tokens and the audio mean side by side as 1024 channels (model.py:185,256), got 2 x %d" % transformer_in_channel)
+        if nhead < 1 or transformer_in_channel % nhead:
+            raise NotImplementedError("nhead = %d does not divide the %d features" % (nhead, transformer_in_channel))
+        if transformer_in_channel // nhead > TOKEN_ENCODER_MAX_HEAD_WIDTH or (transformer_in_channel // nhead) % 4:
+            raise NotImplementedError("nhead = %d gives heads of width %d; the token encoder's attention kernels hold heads up to %d wide, "
+                                      "a multiple of 4" % (nhead, transformer_in_channel // nhead, TOKEN_ENCODER_MAX_HEAD_WIDTH))
+        if num_clips != 32:
+            raise NotImplementedError("the fusion model needs num_clips=32: its positional encoding has 4*7*12+3 rows, the positions of "
+                                      "y0 for a 32-frame clip (model.py:143), got num_clips=%d" % num_clips)
+        self.visual_model = VideoSaliencyModel(transformer_in_channel, nhead, use_upsample, num_hier, num_clips)
+        self.conv_in_1x1 = ConvParams(1024, transformer_in_channel, kernel_size=1, stride=1, bias=True)
+        self.transformer = _TransformerParams(transformer_in_channel, hidden_size=transformer_in_channel, nhead=nhead,
+                                              num_encoder_layers=num_encoder_layers, max_len=self.N_VIDEO_TOKENS + self.N_AUDIO_TOKENS,
+                                              max_head_width=TOKEN_ENCODER_MAX_HEAD_WIDTH)
+        self.audionet = SoundNet()
+        self.audio_conv_1x1 = _Conv2dParams(1024, transformer_in_channel, kernel_size=1, stride=1, bias=True)
+        import os
+        if os.path.isfile(self.soundnet_checkpoint):
+            self.load_soundnet(self.soundnet_checkpoint)
+            print("Loaded SoundNet Weights")
+        else:
+            import sys
+            print("SoundNet weights? (%s not found: default init)" % self.soundnet_checkpoint, file=sys.stderr)
+        self.maxpool = _Marker("maxpool3d", kernel_size=(4, 1, 1), stride=(2, 1, 2), padding=(0, 0, 0))
+        self.bilinear = _BilinearParams(42, 3, 4 * 7 * 12)
+
+    def load_soundnet(self, path="./soundnet8_final.pth"):
+        self.audionet.load_state_dict(torch.load(path, map_location="cpu"))
+
+    def _fwd(self, ctx, x, audio):
+        from . import fusion
+        xv = x.v
+        H, W = x.fold if x.fold is not None else (xv.H, xv.W)
+        if (xv.T, H, W) != (32, 224, 384):
+            raise ValueError("the fusion model runs on 32 x 224 x 384 clips (its 336 position tokens are y0's 4 x 7 x 12 positions, "
+                             "model.py:143,180), got %d x %d x %d" % (xv.T, H, W))
+        a = self.audionet._fwd(ctx, audio)                                # [B, 3, 1, 1, 1024]
+        y0, y1, y2, y3 = self.visual_model.backbone._fwd(ctx, x)          # y0 [B, 4, 7, 12, 1024]
+        assert (a.v.T, a.v.H, a.v.W) == (self.N_AUDIO_TOKENS, 1, 1), "SoundNet gives %d time steps for this waveform, the model has 3 audio tokens" % a.v.T
+        tokens, (vid, aud) = fusion.token_buffer(ctx, xv.B, [(4, 7, 12), (self.N_AUDIO_TOKENS, 1, 1)], self.conv_in_1x1.out_channels)
+        E.conv_forward(ctx, self.conv_in_1x1.plan(), y0, dst=vid)
+        E.conv_forward(ctx, self.audio_conv_1x1.plan(), a, dst=aud)
+        enc = fusion.token_encoder_forward(ctx, self.transformer, tokens)
+        fused = fusion.token_split_forward(ctx, enc, self.N_AUDIO_TOKENS, (4, 7, 12))
+        return self.visual_model.decoder._fwd(ctx, fused, y1, y2, y3)
+
+    def forward(self, x, audio):
+        body = _MapBody(self, self._fwd, video=True, audio=True)
+        return E.run_root(body, [x, audio], list(self.parameters()))[0]
+
+
 class _BilinearParams(nn.Bilinear):
     def forward(self, a, b):  # pragma: no cover
         raise RuntimeError("parameters only")
@@ -370,6 +444,7 @@ class _BilinearParams(nn.Bilinear):
 # --------------------------------------------------------------------------
 
 TRANSFORMER_MAX_HEAD_WIDTH = 96      # the attention kernels' LDS tiles (csrc/transformer.hip)
+TOKEN_ENCODER_MAX_HEAD_WIDTH = 128   # the token encoder's (csrc/token_encoder.hip)
 
 
 def sinusoid_table(n_tokens, n_features):
@@ -415,15 +490,16 @@ class _EncoderStackParams(nn.Module):
 class _TransformerParams(nn.Module):
     """model.py:28-46 with num_decoder_layers=-1, spatial_dim=-1 (all the audio-visual model builds)."""
 
-    def __init__(self, feat_size, hidden_size=256, nhead=4, num_encoder_layers=3, max_len=4):
+    def __init__(self, feat_size, hidden_size=256, nhead=4, num_encoder_layers=3, max_len=4, max_head_width=TRANSFORMER_MAX_HEAD_WIDTH):
         super().__init__()
         if num_encoder_layers < 1:
             raise ValueError("num_encoder_layers must be >= 1, got %d" % num_encoder_layers)
         if nhead < 1 or feat_size % nhead:
             raise ValueError("nhead = %d does not divide the %d features" % (nhead, feat_size))
-        if feat_size // nhead > TRANSFORMER_MAX_HEAD_WIDTH:
-            raise NotImplementedError("nhead = %d gives heads of width %d; the attention kernels hold heads up to %d wide "
-                                      "(nhead = 4 -> 84 is what the reference trains)" % (nhead, feat_size // nhead, TRANSFORMER_MAX_HEAD_WIDTH))
+        if feat_size // nhead > max_head_width:
+            raise NotImplementedError("nhead = %d gives heads of width %d; the attention kernels hold heads up to %d wide%s"
+                                      % (nhead, feat_size // nhead, max_head_width,
+                                         " (nhead = 4 -> 84 is what the reference trains)" if feat_size == 336 else ""))
         self.pos_encoder = _PositionalEncodingParams(feat_size, max_len=max_len)
         self.transformer_encoder = _EncoderStackParams(_EncoderLayerParams(feat_size, nhead, hidden_size), num_encoder_layers)
         self.spatial_dim, self.use_decoder = -1, False

@@ -78,6 +78,10 @@ def build_parser():
                    help="arithmetic of the HIP path.  Default fp32s (split-bf16 products, fp32 tensors): INSIDE the reference contract -- maps within "
                         "1e-3 of the PyTorch-CPU path, exact argmax.  bf16 is the throughput mode (2.9x faster; maps within 2.5e-2, gradients of the "
                         "encoder noisy: DESIGN.md) and must be asked for; fp32 is the exact-fp32-MFMA path")
+    p.add_argument('--token_fusion', default=False, type=_bool,
+                   help="BUILD-DEFINED (the reference's drivers never build this class): with --use_sound True, train "
+                        "VideoAudioSaliencyFusionModel, the token-wise transformer fusion (model.py:116-189; 512 features, so "
+                        "--transformer_in_channel is not consulted; clips of 32 x 224 x 384)")
     p.add_argument('--synthetic_steps', default=20, type=int, help="steps per epoch with --dataset synthetic")
     p.add_argument('--sound_path_data', default="/ssd_scratch/cvit/samyak/data/", type=str,
                    help="root of the audio-visual sets (hard-coded in the reference: dataloader.py:127)")
@@ -109,6 +113,11 @@ class SyntheticClips(torch.utils.data.Dataset):
 
 def build_model(args):
     from . import model
+    if getattr(args, "token_fusion", False):
+        if not args.use_sound:
+            raise ValueError("--token_fusion True needs --use_sound True (the fusion model reads the waveform)")
+        return model.VideoAudioSaliencyFusionModel(nhead=args.nhead, num_encoder_layers=args.num_encoder_layers,
+                                                   use_upsample=bool(args.decoder_upsample), num_hier=args.num_hier, num_clips=args.clip_size)
     if args.use_sound:
         return model.VideoAudioSaliencyModel(
             transformer_in_channel=args.transformer_in_channel, nhead=args.nhead, use_transformer=args.use_transformer,
