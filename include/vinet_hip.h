@@ -350,7 +350,9 @@ int vinet_channel_sum(const VinetTensor* x, int32_t dtype, float* workspace, int
  * MaxPool2d (k,1) of SoundNet model.py:753,759,774 with T as the pooled axis).
  * -inf padding, first maximum in (t,h,w) scan order wins ties.  `argmax`
  * (optional, uint8 [B][oT][oH][oW][C] dense) holds the window-relative tap
- * index for the backward gather.
+ * index for the backward gather.  `pre` has a scale AND a shift, or neither:
+ * a scale with a NULL shift is rejected (both entry points and the name query
+ * return -1 before any route or launch).
  * ---------------------------------------------------------------------- */
 typedef struct VinetPoolDesc {
   int32_t dtype;

@@ -590,6 +590,9 @@ class AbiEmulator:
     # -- pooling / upsample ---------------------------------------------------------
     def vinet_maxpool3d(self, d, x, pre, y, argmax, stream):
         d, x, y = _deref(d), _deref(x), _deref(y)
+        if pre.scale and not pre.shift:
+            self.err = b"maxpool3d: a pre with a scale needs a shift"
+            return -1
         xa = affine(rd(x, d.dtype), pre, x.C)
         if d.dtype != F32 and pre.scale:
             # pooling sees the pending affine applied AND rounded to the activation dtype (pool.hip: pool_round)

@@ -263,8 +263,9 @@ POOL_TABLE = [
     ('cols65535_k311_bf16', T3, BF16, C65535, ONE, 'affine_relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd8_kernel<bf16>'),
     ('pk0_lds2', K3, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_pk=0, pool_lds=2), 'maxpool_k3s1_lds_kernel<bf16>', 'maxpool_bwd_k3s1_kernel<bf16>'),
     ('pk0_k133s2', P0, BF16, SM, OCT, 'affine_relu', 'ok', dict(pool_pk=0), 'maxpool_fwd8_kernel<bf16>', 'maxpool_bwd_k133s2_kernel<bf16>'),
-    ('scale_only_lds2', K3, BF16, SM, OCT, 'scale_only', 'ok', dict(pool_lds=2), 'maxpool_k3s1_lds_kernel<bf16>', 'maxpool_bwd_k3s1_kernel<bf16>'),
-    ('scale_only_k133s2', P0, BF16, SM, OCT, 'scale_only', 'ok', dict(), 'maxpool_fwd8_kernel<bf16>', 'maxpool_bwd_k133s2_kernel<bf16>'),
+    # a scale without a shift: every kernel would read shift[c] through the null pointer, so the forward is rejected (None); the backward has no pre
+    ('scale_only_lds2', K3, BF16, SM, OCT, 'scale_only', 'ok', dict(pool_lds=2), None, 'maxpool_bwd_k3s1_kernel<bf16>'),
+    ('scale_only_k133s2', P0, BF16, SM, OCT, 'scale_only', 'ok', dict(), None, 'maxpool_bwd_k133s2_kernel<bf16>'),
     ('no_pre_lds2', K3, BF16, SM, OCT, 'none', 'ok', dict(pool_lds=2), 'maxpool_k3s1_pk_kernel', 'maxpool_bwd_k3s1_kernel<bf16>'),
     ('relu_only_k133s2', P0, BF16, SM, OCT, 'relu', 'ok', dict(), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k133s2_kernel<bf16>'),
     ('t1_lds2', K3, BF16, (2, 1, 9, 10), OCT, 'affine_relu', 'ok', dict(pool_lds=2, pool_twalk=2), 'maxpool_fwd8_pk_kernel', 'maxpool_bwd_k3s1_tw3_kernel'),

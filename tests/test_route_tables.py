@@ -162,7 +162,7 @@ def test_pool_table_names_every_instantiation_of_pool_hip():
     assert len(typed) == len(set(typed)) == 11 and len(plain) == len(set(plain)) == 3      # DISPATCH_T: two dtypes per typed site
     inst = {"%s<%s>" % (k, t) for k in typed for t in ("f32", "bf16")} | set(plain)
     assert len(inst) == 25 and len([n for n in inst if "_bwd" in n]) == 13
-    assert {c[8] for c in R.POOL_TABLE} | {c[9] for c in R.POOL_TABLE} - {None} == inst
+    assert ({c[8] for c in R.POOL_TABLE} | {c[9] for c in R.POOL_TABLE}) - {None} == inst      # (None: a rejected call)
     assert len({c[0] for c in R.POOL_TABLE}) == len(R.POOL_TABLE)
     for opt, values in (("pool_lds", {0, 1, 2}), ("pool_pk", {0, 1}), ("pool_twalk", {0, 1, 2, 3}), ("pool_blk", {0, 1})):      # every documented value
         assert {c[7].get(opt, G.OPT_DEFAULTS[opt]) for c in R.POOL_TABLE} == values, opt

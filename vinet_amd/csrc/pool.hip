@@ -1049,10 +1049,10 @@ static bool pool_oct(const VinetTensor& a, const VinetTensor& b, const uint8_t* 
   return oct_ok(a) && oct_ok(b) && ((uintptr_t)argmax % 8) == 0;
 }
 
-static PoolRoute pool_fwd_route(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y, const uint8_t* argmax) {
+static PoolRoute pool_fwd_route(const VinetPoolDesc* d, const VinetTensor* x, const VinetTensor* y, const uint8_t* argmax) {
   const bool oct = pool_oct(*x, *y, argmax);
   const bool walk_t = d->kT == 3 && d->sT == 1 && d->pT == 1 && y->T == x->T && x->T >= 2;      // T-walking kernels: any in-plane window
-  const bool pk = d->dtype == VINET_BF16 && g_vinet_opt_pool_pk && (!pre.scale || pre.shift);      // bf16 on packed keys
+  const bool pk = d->dtype == VINET_BF16 && g_vinet_opt_pool_pk;      // bf16 on packed keys
   const long cols8 = (long)y->B * y->H * y->W * (y->C / 8);
   if (pool_is_k3s1(d, *x, *y) && walk_t && oct && g_vinet_opt_pool_lds && (g_vinet_opt_pool_lds >= 2 || cols8 >= POOL_FILL_COLS)) {
     const int tilesH = (y->H + 7) / 8, tilesW = (y->W + 7) / 8;
@@ -1098,9 +1098,11 @@ static PoolRoute pool_bwd_route(const VinetPoolDesc* d, const VinetTensor* dy, c
   return {POOL_BWD, "maxpool_bwd_kernel", true, view_voxels(*dx) * (dx->C / 4)};
 }
 
-static int pool_fwd_args(const VinetPoolDesc* d, const VinetTensor* x, const VinetTensor* y) {
+static int pool_fwd_args(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y) {
   VN_CHECK_ARG(d && x && y && quad_ok(*x, esize(d->dtype)) && quad_ok(*y, esize(d->dtype)) && x->C == y->C && x->B == y->B,
                "maxpool3d: bad views");
+  // every kernel reads shift[c] wherever scale is set: a scale alone would be a read through a null pointer
+  VN_CHECK_ARG(!(pre.scale && !pre.shift), "maxpool3d: a pre with a scale needs a shift");
   VN_CHECK_ARG(d->kT * d->kH * d->kW <= 255 && d->kT > 0 && d->kH > 0 && d->kW > 0, "maxpool3d: window too large");
   return 0;
 }
@@ -1117,8 +1119,8 @@ static int pool_kernel_name(const PoolRoute& r, int dtype, char* buf, int32_t n)
 
 extern "C" int vinet_maxpool3d_kernel_name(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
                                            const uint8_t* argmax, char* buf, int32_t n) {
-  if (!buf || n <= 0 || pool_fwd_args(d, x, y)) return -1;
-  return pool_kernel_name(pool_fwd_route(d, x, pre, y, argmax), d->dtype, buf, n);
+  if (!buf || n <= 0 || pool_fwd_args(d, x, pre, y)) return -1;
+  return pool_kernel_name(pool_fwd_route(d, x, y, argmax), d->dtype, buf, n);
 }
 extern "C" int vinet_maxpool3d_bwd_kernel_name(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax,
                                                const VinetTensor* dx, char* buf, int32_t n) {
@@ -1128,8 +1130,8 @@ extern "C" int vinet_maxpool3d_bwd_kernel_name(const VinetPoolDesc* d, const Vin
 
 extern "C" int vinet_maxpool3d(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
                                uint8_t* argmax, void* stream) {
-  if (pool_fwd_args(d, x, y)) return -1;
-  const PoolRoute r = pool_fwd_route(d, x, pre, y, argmax);
+  if (pool_fwd_args(d, x, pre, y)) return -1;
+  const PoolRoute r = pool_fwd_route(d, x, y, argmax);
   const PoolP p = make_poolp(d);
   const TView xv = make_view(*x), yv = make_view(*y);
   const Affine a = make_affine(pre);
