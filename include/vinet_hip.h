@@ -315,13 +315,18 @@ int vinet_bn_fold(const float* gamma, const float* beta, const float* running_me
                   const float* conv_bias /* optional */, float eps, int32_t C, float* scale, float* shift,
                   float* invstd /* optional */, void* stream);
 /* Generic per-channel statistics of a tensor (used when the producer is not a
- * conv epilogue): partials [rows][2][C]; returns rows via vinet_stats_rows. */
+ * conv epilogue): partials [rows][2][C]; returns rows via vinet_stats_rows.
+ * Refused (vinet_channel_stats, vinet_bn_bwd_reduce, vinet_channel_sum alike): more than 256 channel groups that do not fill
+ * whole passes of 256 -- groups of 8 channels when every view has C, ld and sB in multiples of 8 and a 16-byte aligned pointer
+ * (C > 2048 with C % 2048 != 0), groups of 4 otherwise (C > 1024 with C % 1024 != 0).  The network has nothing past 2048. */
 int vinet_channel_stats(const VinetTensor* x, int32_t dtype, float* partials, void* stream);
 int vinet_stats_rows(const VinetTensor* x);
 /* Backward of y = relu?(scale*x_raw + shift) followed by BN-train statistics:
  *  pass 1: partials[rows][2][C] of (sum dz*mask, sum dz*mask*xhat)
  *  pass 2: dx_raw = scale*(dz*mask - c1 - xhat*c2)   (c1 = c2 = 0 in eval mode)
- * native_batch_norm_backward + threshold_backward (train.py:216). */
+ * native_batch_norm_backward + threshold_backward (train.py:216).
+ * vinet_bn_bwd_reduce: fwd.scale and fwd.shift come together or not at all (one without the other is refused); with neither and
+ * relu = 1 the gate is x_raw > 0. */
 int vinet_bn_bwd_reduce(const VinetTensor* dz, const VinetTensor* x_raw, int32_t dtype, VinetAffine fwd,
                         const float* mean, const float* invstd, float* partials, void* stream);
 int vinet_bn_bwd_finalize(const float* partials, int32_t rows, int32_t C, int32_t ld, double count, const float* scale,

@@ -468,8 +468,10 @@ class AbiEmulator:
     # -- BN ----------------------------------------------------------------------
     def vinet_bn_partials_fold(self, partials, rows, Cc, out, out_rows, stream):
         per = (rows + out_rows - 1) // out_rows
-        assert (out_rows - 1) * per < rows
-        P = _f32(partials, rows * 2 * Cc).reshape(rows, 2, Cc).astype(np.float64)
+        if (out_rows - 1) * per >= rows:
+            self.err = b"bn_partials_fold: out_rows=%d leaves empty chunks for rows=%d" % (out_rows, rows)
+            return -1
+        P =_f32(partials, rows * 2 * Cc).reshape(rows, 2, Cc).astype(np.float64)
         O = _f32(out, out_rows * 2 * Cc).reshape(out_rows, 2, Cc)
         for i in range(out_rows):
             O[i] = P[i * per:(i + 1) * per].sum(0)
@@ -519,8 +521,22 @@ class AbiEmulator:
         n = x.B * x.T * x.H * x.W
         return max(1, min(1024, (n + 63) // 64))
 
+    def _ragged_groups(self, dtype, *views):
+        """csrc/bn.hip, launch_channel_reduce: more than 256 channel groups (of 8; of 4 unless every view is 8-channel eligible) that
+        do not fill whole passes of 256 are refused"""
+        Cc = views[0].C
+        oct_ = all(t.C % 8 == 0 and t.ld % 8 == 0 and t.sB % 8 == 0 and t.ptr % 16 == 0 for t in views)
+        groups = Cc // (8 if oct_ else 4)
+        if groups > 256 and groups % 256:
+            self.err = b"channel reduction: C=%d leaves a ragged pass of the %d-channel group loop (more than 256 groups, no multiple of 256)" % (
+                Cc, 8 if oct_ else 4)
+            return True
+        return False
+
     def vinet_channel_stats(self, x, dtype, partials, stream):
         x = _deref(x)
+        if self._ragged_groups(dtype, x):
+            return -1
         rows = self.vinet_stats_rows(x)
         v = rd(x, dtype).reshape(-1, x.C).astype(np.float64)
         P = _f32(partials, rows * 2 * x.C).reshape(rows, 2, x.C)
@@ -533,13 +549,19 @@ class AbiEmulator:
         xv = rd(x_raw, dtype)
         g = rd(dz, dtype)
         if fwd.relu:
-            z = xv * _f32(fwd.scale, Cc) + _f32(fwd.shift, Cc) if fwd.scale else xv
+            # (in float64: the product of two fp32 values is exact there and the rounded sum keeps its sign -- the kernels' fmaf(...) > 0)
+            z = xv.astype(np.float64) * _f32(fwd.scale, Cc) + _f32(fwd.shift, Cc) if fwd.scale else xv
             g = g * (z > 0)
         xhat = (xv - _f32(mean, Cc)) * _f32(invstd, Cc)
         return g, xhat
 
     def vinet_bn_bwd_reduce(self, dz, x_raw, dtype, fwd, mean, invstd, partials, stream):
         dz, x_raw = _deref(dz), _deref(x_raw)
+        if bool(fwd.scale) != bool(fwd.shift):
+            self.err = b"bn_bwd_reduce: a forward affine needs both its scale and its shift"
+            return -1
+        if self._ragged_groups(dtype, x_raw, dz):
+            return -1
         g, xhat = self._bn_bwd_terms(dz, x_raw, dtype, fwd, mean, invstd)
         rows = self.vinet_stats_rows(x_raw)
         P = _f32(partials, rows * 2 * x_raw.C).reshape(rows, 2, x_raw.C)
@@ -582,7 +604,15 @@ class AbiEmulator:
 
     def vinet_channel_sum(self, x, dtype, workspace, Cout, out, accumulate, stream):
         x = _deref(x)
-        s = rd(x, dtype).reshape(-1, x.C).astype(np.float64).sum(0).reshape(-1, Cout).sum(0)
+        if x.C % Cout:
+            self.err = b"channel_sum: bad arguments"
+            return -1
+        if self._ragged_groups(dtype, x):
+            return -1
+        self.vinet_channel_stats(x, dtype, workspace, stream)          # the workspace receives the partials table, as in the library
+        rows = self.vinet_stats_rows(x)
+        P = _f32(workspace, rows * 2 * x.C).reshape(rows, 2, x.C).astype(np.float64)
+        s = P[:, 0].sum(0).reshape(-1, Cout).sum(0)
         o = _f32(out, Cout)
         o[:] = o + s if accumulate else s
         return 0

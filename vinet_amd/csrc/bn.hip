@@ -383,11 +383,20 @@ __global__ __launch_bounds__(64) void channel_reduce_small_kernel(TView x, TView
   partials[x.C + c] = p;
 }
 
+// The group loops of channel_reduce8_kernel, bn_bwd_reduce8_bf16_kernel and channel_reduce_kernel hold two barriers: every
+// lane of a workgroup has to take the same number of trips, i.e. the groups (of 8 channels, of 4 on the quad route) either fit
+// one pass of 256 lanes or fill whole passes.  Nothing in the network is wider than 2048 channels; anything else is refused.
+static inline bool groups_uniform(int groups) { return groups <= 256 || groups % 256 == 0; }
+
 template <int MODE>
 static int launch_channel_reduce(const VinetTensor* x, const VinetTensor* dz, int dtype, VinetAffine fwd,
                                  const float* mean, const float* invstd, float* partials, void* stream) {
   const long nvox = view_voxels(*x);
   const int rows = stats_rows_for(nvox);
+  const bool oct = oct_ok(*x) && (!dz || oct_ok(*dz));
+  VN_CHECK_ARG(groups_uniform(oct ? x->C / 8 : x->C / 4),
+               "channel reduction: C=%d leaves a ragged pass of the %d-channel group loop (more than 256 groups, no multiple of 256)",
+               x->C, oct ? 8 : 4);
   if (g_vinet_opt_reduce_small && nvox <= 64 && rows == 1) {
     const TView xs = make_view(*x), ds = dz ? make_view(*dz) : xs;
     DISPATCH_T(dtype, T, hipLaunchKernelGGL((channel_reduce_small_kernel<T, MODE>), dim3((x->C + 63) / 64), dim3(64), 0,
@@ -407,7 +416,7 @@ static int launch_channel_reduce(const VinetTensor* x, const VinetTensor* dz, in
                          invstd, nvox, g_vinet_opt_reduce_il ? 0 : vb, partials);
     return vn_launch_status("bn_bwd_reduce8_bf16");
   }
-  if (oct_ok(*x) && (!dz || oct_ok(*dz))) {
+  if (oct) {
     DISPATCH_T(dtype, T, hipLaunchKernelGGL((channel_reduce8_kernel<T, MODE>), dim3(rows), dim3(256), 0,
                                             (hipStream_t)stream, xv, dv, make_affine(fwd), mean, invstd, nvox, g_vinet_opt_reduce_il ? 0 : vb, partials);)
     return vn_launch_status("channel_reduce8");
@@ -427,6 +436,9 @@ extern "C" int vinet_bn_bwd_reduce(const VinetTensor* dz, const VinetTensor* x_r
                                    const float* mean, const float* invstd, float* partials, void* stream) {
   VN_CHECK_ARG(dz && x_raw && partials && mean && invstd && quad_ok(*dz, esize(dtype)) && quad_ok(*x_raw, esize(dtype)) &&
                    same_dims(*dz, *x_raw), "bn_bwd_reduce: bad arguments");
+  // (the 4-channel kernel reads the shift wherever there is a scale and ignores a shift without one; the other kernels gate on
+  //  x * (scale or 1) + (shift or 0): one contract for all of them -- both or neither)
+  VN_CHECK_ARG((fwd.scale != nullptr) == (fwd.shift != nullptr), "bn_bwd_reduce: a forward affine needs both its scale and its shift");
   return launch_channel_reduce<1>(x_raw, dz, dtype, fwd, mean, invstd, partials, stream);
 }
 
