@@ -373,6 +373,21 @@ int vinet_maxpool3d_kernel_name(const VinetPoolDesc* d, const VinetTensor* x, Vi
                                 const uint8_t* argmax, char* buf, int32_t n);
 int vinet_maxpool3d_bwd_kernel_name(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax,
                                     const VinetTensor* dx, char* buf, int32_t n);
+/* BatchNorm backward behind the 1x3x3 / s(1,2,2) / p(0,1,1) pool, the pool's backward folded in: the gradient dz behind
+ * relu(bn(z)) is never stored.  Both passes form it in registers exactly as vinet_maxpool3d_bwd(pool, dp, argmax, gacc, accumulate)
+ * would have stored it (bf16, + the old contents of `gacc` when `accumulate`) and continue as vinet_bn_bwd_reduce /
+ * vinet_bn_bwd_apply: the partials have vinet_stats_rows(z) rows of [2][C] for vinet_bn_bwd_finalize (the same terms as the unfused
+ * reduce, partitioned differently), dx is bit-identical to the three-call chain.  dx may be gacc (in place); gacc may be NULL
+ * without `accumulate`.  vinet_bn_bwd_pool_ok: 1 if the two entry points take this problem -- bf16, C in whole groups of 8 on
+ * 16-byte views, that pool geometry, dp the pooled shape of z, dx the shape of z -- else 0 with the reason in vinet_last_error;
+ * the entry points themselves return -1 on such a problem and launch nothing. */
+int vinet_bn_bwd_pool_ok(const VinetPoolDesc* pool, const VinetTensor* z, const VinetTensor* dp, const VinetTensor* dx, int32_t dtype);
+int vinet_bn_bwd_reduce_pool(const VinetPoolDesc* pool, const VinetTensor* dp, const uint8_t* argmax, const VinetTensor* gacc,
+                             int32_t accumulate, const VinetTensor* z, int32_t dtype, VinetAffine fwd, const float* mean,
+                             const float* invstd, float* partials, void* stream);
+int vinet_bn_bwd_apply_pool(const VinetPoolDesc* pool, const VinetTensor* dp, const uint8_t* argmax, const VinetTensor* gacc,
+                            int32_t accumulate, const VinetTensor* z, int32_t dtype, VinetAffine fwd, const float* mean,
+                            const float* invstd, const float* c1, const float* c2, const VinetTensor* dx, void* stream);
 
 /* nn.Upsample(scale_factor=(1,2,2), mode='trilinear', align_corners=False)
  * (model.py:254,258,263,268,273,278) and its backward. */

@@ -101,6 +101,9 @@ SIGNATURES = {
     "vinet_bn_bwd_finalize": [_vp, _i32, _i32, _i32, _f64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "vinet_bn_bwd_apply": [_PT, _PT, _i32, CAffine, _vp, _vp, _vp, _vp, _PT, _vp],
     "vinet_bn_bwd_apply_split": [_PT, _PT, CAffine, _vp, _vp, _vp, _vp, _PT, _PT, _PT, _vp],
+    "vinet_bn_bwd_pool_ok": [_PP, _PT, _PT, _PT, _i32],
+    "vinet_bn_bwd_reduce_pool": [_PP, _PT, _vp, _PT, _i32, _PT, _i32, CAffine, _vp, _vp, _vp, _vp],
+    "vinet_bn_bwd_apply_pool": [_PP, _PT, _vp, _PT, _i32, _PT, _i32, CAffine, _vp, _vp, _vp, _vp, _PT, _vp],
     "vinet_act_bwd": [_PT, _i32, _PT, _i32, _i32, _PT, _i32, _vp],
     "vinet_channel_sum": [_PT, _i32, _vp, _i32, _vp, _i32, _vp],
     "vinet_maxpool3d": [_PP, _PT, CAffine, _PT, _vp, _vp],

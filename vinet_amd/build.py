@@ -29,7 +29,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.j
 # the asm owns (conv_pw.h: the global-load ring with counted vmcnt; pool.hip: routing on the EXEC mask).  A vector-register spill
 # in one of them would read in-flight data: the build FAILS on it instead of shipping silently wrong kernels.  Checked from
 # hipcc's own -Rpass-analysis=kernel-resource-usage remarks of the same compilation (pinned toolchain: ROCm 7.2 / clang 22).
-GUARDED = {"conv_bf16.hip": ("conv_pw_kernel",), "pool.hip": ("maxpool_bwd",), "conv_bnb.hip": ()}     # (conv_bnb.hip: resource table only)
+GUARDED = {"conv_bf16.hip": ("conv_pw_kernel",), "pool.hip": ("maxpool_bwd",), "bn.hip": ("bn_bwd_reduce_pool", "bn_bwd_apply_pool"),
+           "conv_bnb.hip": ()}     # (conv_bnb.hip: resource table only)
 RESOURCES = os.path.join(CSRC, "obj", "kernel_resources.json")
 
 

@@ -1,6 +1,7 @@
 // BatchNorm3d / 2d kernels (train and eval, model_utils.py:132,145,149): per-channel statistics and their fold into a
 // pending scale / shift, backward reduce + finalize + apply, activation backward, per-channel sums (conv bias gradients).
 #include "elementwise.h"
+#include "pool_gather.h"
 
 // ============================================================================
 // BatchNorm
@@ -677,6 +678,272 @@ extern "C" int vinet_bn_bwd_apply_split(const VinetTensor* dz, const VinetTensor
   hipLaunchKernelGGL((bn_bwd_apply8_kernel<float, true>), dim3((unsigned)((nvox + vb - 1) / vb)), dim3(256), 0, (hipStream_t)stream,
                      make_view(*dz), make_view(*x_raw), make_affine(fwd), mean, invstd, c1, c2, make_view(*dx), make_view(*hi), make_view(*lo), nvox, vb);
   return vn_launch_status("bn_bwd_apply8<split>");
+}
+
+// ---- BatchNorm backward behind a 1x3x3 / s(1,2,2) / p(0,1,1) max-pool: the pool's backward folded into both passes -------------
+// The gradient dz behind relu(bn(z)) is the pool's backward of dp (+ what the gradient buffer `gacc` already holds, when
+// accumulating).  Written out by maxpool_bwd_k133s2_kernel it is stored once and read by the reduce and by the apply pass; here both
+// passes form it in registers from dp (a quarter of the positions), the argmax bytes and gacc.  A lane owns one 2 x 2 input block x 8
+// channels per trip, as in the pool kernel, and forms dz EXACTLY as that kernel stores it -- fp32 sum over the windows q = 0...3 in
+// that order, + old, rounded to bf16 by the same conversion -- then continues with the arithmetic of bn_bwd_reduce8_bf16_kernel /
+// bn_bwd_apply8_bf16_kernel on the rounded value: the apply's result is bit-identical to the three-kernel chain, the reduce's
+// partial rows hold the same terms under another partition (rows of blocks instead of rows of voxels).
+// Both are HBM-bound kernels of the lean class (see bn_bwd_reduce8_bf16_kernel): 128 registers at most, four waves per SIMD.
+
+// argmax words and packed dp rows of the four windows that reach block (hb, wb); a window past the edge carries no tap code, its
+// row is read from window (hb, wb), which always exists, and never added
+VN_DEV void bn_pool_windows(const TView& dp, const uint8_t* __restrict__ argmax, int b, int t, int hb, int wb, int g,
+                            unsigned long long am[4], uint4 dv[4]) {
+  bool wok[4];
+  pool_k133s2_codes(dp, argmax, b, t, hb, wb, g, am, wok);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int ho = wok[q] ? hb + (q >> 1) : hb, wo = wok[q] ? wb + (q & 1) : wb;
+    dv[q] = *(const uint4*)((const bf16_t*)dp.p + vox_off(dp, b, t, ho, wo) + g * 8);
+  }
+}
+// dz of input (ih, iw) of the block as four packed bf16 pairs: what maxpool_bwd_k133s2_kernel stores there
+template <bool ACC>
+VN_DEV void bn_pool_dz(const unsigned long long am[4], const uint4 dv[4], int ih, int iw, const uint4& old, uint32_t dzw[4]) {
+  float gr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long ex;                                  // (the lanes of this region: POOL_ADD_IF restores this mask)
+  asm volatile("s_mov_b64 %0, exec" : "=s"(ex));
+  pool_k133s2_sum_pk(am, dv, ih, iw, ex, gr);
+  if (ACC) {
+    float o[8];
+    unpack16<bf16_t>(old, o);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gr[e] += o[e];
+  }
+#pragma unroll
+  for (int h = 0; h < 4; ++h) dzw[h] = pack2bf(gr[2 * h], gr[2 * h + 1]);
+}
+
+// partials contract of bn_bwd_reduce8_bf16_kernel ([gridDim.x][2][C], every row written); the rows partition the 2 x 2 blocks
+// [B][T][HB][WB] (vb blocks each, or interleaved rounds of R blocks when vb == 0)
+template <bool ACC>
+__global__ __launch_bounds__(256, 4) void bn_bwd_reduce_pool_kernel(TView x, TView dp, const uint8_t* __restrict__ argmax, TView gacc,
+                                                                    Affine fwd, const float* mean, const float* invstd, FastDiv dWB,
+                                                                    FastDiv dHB, long nblk, long vb, float* __restrict__ partials) {
+  const int G = x.C / 8;
+  const int Gb = G;
+  const int R = 256 / Gb;
+  const int r = threadIdx.x / Gb;
+  const int g0 = threadIdx.x % Gb;
+  __shared__ float red[256 * 16];
+  const long v0 = vb ? (long)blockIdx.x * vb : (long)blockIdx.x * R;
+  long v1 = vb ? v0 + vb : nblk; if (v1 > nblk) v1 = nblk;
+  const long vstep = vb ? (long)R : (long)gridDim.x * R;
+  const bool relu = fwd.relu != 0;
+  const int g = g0;                                       // (at most 256 groups: bn_bwd_pool_args)
+  {
+    float s[8], p[8], mu[8], is[8], sc[8], sh[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { s[e] = 0.f; p[e] = 0.f; mu[e] = 0.f; is[e] = 1.f; sc[e] = 1.f; sh[e] = 0.f; }
+    if (r < R) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { mu[e] = mean[g * 8 + e]; is[e] = invstd[g * 8 + e]; }
+      if (relu) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { sc[e] = fwd.scale ? fwd.scale[g * 8 + e] : 1.f; sh[e] = fwd.shift ? fwd.shift[g * 8 + e] : 0.f; }
+      }
+      for (long v = v0 + r; v < v1; v += vstep) {
+        int b, t, hb, wb;
+        decode_m((int)v, dWB, dHB, x.dT, b, t, hb, wb);
+        const int h0 = 2 * hb, w0 = 2 * wb;
+        unsigned long long am[4];
+        uint4 dv[4];
+        bn_pool_windows(dp, argmax, b, t, hb, wb, g, am, dv);
+#pragma unroll
+        for (int ih = 0; ih < 2; ++ih) {                    // one input row of the block at a time: two voxels of z (and of gacc) in flight
+          if (h0 + ih >= x.H) continue;
+          const bool in1 = w0 + 1 < x.W;                    // (clamped to the row's first input: the load is unconditional, the use is not)
+          // (row offsets of z and gacc share the in-image part: one voxel index, two strides)
+          const long vi = (long)(t * x.H + h0 + ih) * x.W + w0;
+          const bf16_t* xp = (const bf16_t*)x.p + (long)b * x.sB + vi * x.ld + g * 8;
+          const bf16_t* op = (const bf16_t*)gacc.p + (long)b * gacc.sB + vi * gacc.ld + g * 8;
+          uint4 xr[2], og[2];
+#pragma unroll
+          for (int iw = 0; iw < 2; ++iw) {
+            xr[iw] = ld16_nt(xp + (in1 ? iw * x.ld : 0));
+            if (ACC) og[iw] = ld16_nt(op + (in1 ? iw * gacc.ld : 0));
+            else og[iw] = make_uint4(0, 0, 0, 0);
+          }
+#pragma unroll
+          for (int iw = 0; iw < 2; ++iw) {
+            if (iw && !in1) continue;
+            uint32_t gw[4];
+            bn_pool_dz<ACC>(am, dv, ih, iw, og[iw], gw);
+            const uint32_t xw[4] = {xr[iw].x, xr[iw].y, xr[iw].z, xr[iw].w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const float xv = __uint_as_float((e & 1) ? (xw[e >> 1] & 0xffff0000u) : (xw[e >> 1] << 16));
+              float gg = __uint_as_float((e & 1) ? (gw[e >> 1] & 0xffff0000u) : (gw[e >> 1] << 16));
+              if (relu && !(fmaf(xv, sc[e], sh[e]) > 0.f)) gg = 0.f;
+              s[e] += gg;
+              p[e] += gg * (xv - mu[e]) * is[e];
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (r < R) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { red[threadIdx.x * 16 + e] = s[e]; red[threadIdx.x * 16 + 8 + e] = p[e]; }
+    }
+    __syncthreads();
+    if (r == 0) {
+      for (int rr = 1; rr < R; ++rr)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { s[e] += red[(rr * Gb + g0) * 16 + e]; p[e] += red[(rr * Gb + g0) * 16 + 8 + e]; }
+      float* o = partials + (long)blockIdx.x * 2 * x.C + g * 8;
+      *(float4*)o = make_float4(s[0], s[1], s[2], s[3]);
+      *(float4*)(o + 4) = make_float4(s[4], s[5], s[6], s[7]);
+      *(float4*)(o + x.C) = make_float4(p[0], p[1], p[2], p[3]);
+      *(float4*)(o + x.C + 4) = make_float4(p[4], p[5], p[6], p[7]);
+    }
+  }
+}
+
+// dx may be gacc (in place): a lane reads the four old values of its block before it stores the first result, and no other lane
+// touches that block
+template <bool ACC>
+__global__ __launch_bounds__(256, 4) void bn_bwd_apply_pool_kernel(TView x, TView dp, const uint8_t* __restrict__ argmax, TView gacc,
+                                                                   Affine fwd, const float* mean, const float* invstd, const float* c1,
+                                                                   const float* c2, TView dx, FastDiv dWB, FastDiv dHB, long nblk, long vb) {
+  const int G = x.C / 8;
+  const int Gb = G;
+  const int R = 256 / Gb;
+  const int r = threadIdx.x / Gb;
+  const int g0 = threadIdx.x % Gb;
+  if (r >= R) return;
+  const long v0 = (long)blockIdx.x * vb;
+  long v1 = v0 + vb; if (v1 > nblk) v1 = nblk;
+  const bool relu = fwd.relu != 0;
+  const int g = g0;                                       // (at most 256 groups: bn_bwd_pool_args)
+  {
+    float A[8], Bc[8], D[8], sh[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = g * 8 + e;
+      const float sc = fwd.scale[c], k = sc * invstd[c] * c2[c];
+      A[e] = sc; Bc[e] = -k; D[e] = fmaf(k, mean[c], -sc * c1[c]);
+      sh[e] = fwd.shift[c];
+    }
+    for (long v = v0 + r; v < v1; v += R) {
+      int b, t, hb, wb;
+      decode_m((int)v, dWB, dHB, x.dT, b, t, hb, wb);
+      const int h0 = 2 * hb, w0 = 2 * wb;
+      unsigned long long am[4];
+      uint4 dv[4];
+      bn_pool_windows(dp, argmax, b, t, hb, wb, g, am, dv);
+#pragma unroll
+      for (int ih = 0; ih < 2; ++ih) {
+        if (h0 + ih >= x.H) continue;
+        const bool in1 = w0 + 1 < x.W;
+        const long vi = (long)(t * x.H + h0 + ih) * x.W + w0;
+        const bf16_t* xp = (const bf16_t*)x.p + (long)b * x.sB + vi * x.ld + g * 8;
+        const bf16_t* op = (const bf16_t*)gacc.p + (long)b * gacc.sB + vi * gacc.ld + g * 8;
+        bf16_t* yp = (bf16_t*)dx.p + (long)b * dx.sB + vi * dx.ld + g * 8;
+        uint4 xr[2], og[2];
+#pragma unroll
+        for (int iw = 0; iw < 2; ++iw) {
+          xr[iw] = ld16_nt(xp + (in1 ? iw * x.ld : 0));
+          if (ACC) og[iw] = *(const uint4*)(op + (in1 ? iw * gacc.ld : 0));
+          else og[iw] = make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int iw = 0; iw < 2; ++iw) {
+          if (iw && !in1) continue;
+          uint32_t gw[4], ow[4];
+          bn_pool_dz<ACC>(am, dv, ih, iw, og[iw], gw);
+          const uint32_t xw[4] = {xr[iw].x, xr[iw].y, xr[iw].z, xr[iw].w};
+#pragma unroll
+          for (int h = 0; h < 4; ++h) {
+            float o2[2];
+#pragma unroll
+            for (int k2 = 0; k2 < 2; ++k2) {
+              const int e = 2 * h + k2;
+              const float xv = __uint_as_float(k2 ? (xw[h] & 0xffff0000u) : (xw[h] << 16));
+              float gg = __uint_as_float(k2 ? (gw[h] & 0xffff0000u) : (gw[h] << 16));
+              if (relu && !(fmaf(xv, A[e], sh[e]) > 0.f)) gg = 0.f;
+              o2[k2] = fmaf(A[e], gg, fmaf(Bc[e], xv, D[e]));
+            }
+            ow[h] = pack2bf(o2[0], o2[1]);
+          }
+          st16_nt(yp + iw * dx.ld, make_uint4(ow[0], ow[1], ow[2], ow[3]));
+        }
+      }
+    }
+  }
+}
+
+// what the two kernels above can do: bf16, whole groups of 8 channels on 16-byte views, the 1x3x3 / (1,2,2) / (0,1,1) geometry
+static int bn_bwd_pool_args(const char* who, const VinetPoolDesc* d, const VinetTensor* z, const VinetTensor* dp, const VinetTensor* dx,
+                            int32_t dtype) {
+  VN_CHECK_ARG(d && z && dp && dx, "%s: null argument", who);
+  VN_CHECK_ARG(dtype == VINET_BF16 && d->dtype == VINET_BF16, "%s: bf16 only (dtype %d, pool dtype %d)", who, dtype, d->dtype);
+  VN_CHECK_ARG(d->kT == 1 && d->kH == 3 && d->kW == 3 && d->sT == 1 && d->sH == 2 && d->sW == 2 && d->pT == 0 && d->pH == 1 && d->pW == 1,
+               "%s: pool %dx%dx%d / s(%d,%d,%d) / p(%d,%d,%d) is not the 1x3x3 / s(1,2,2) / p(0,1,1) pool", who, d->kT, d->kH, d->kW,
+               d->sT, d->sH, d->sW, d->pT, d->pH, d->pW);
+  VN_CHECK_ARG(z->C > 0 && z->C % 8 == 0, "%s: C=%d is not a whole number of 8-channel groups", who, z->C);
+  VN_CHECK_ARG(oct_ok(*z) && oct_ok(*dp) && oct_ok(*dx), "%s: views off the 16-byte, 8-channel grid", who);
+  VN_CHECK_ARG(same_dims(*z, *dx), "%s: z and dx differ in their dims", who);
+  VN_CHECK_ARG(dp->B == z->B && dp->C == z->C && dp->T == z->T && dp->H == (z->H - 1) / 2 + 1 && dp->W == (z->W - 1) / 2 + 1,
+               "%s: dp [%d,%d,%d,%d,%d] is not the pooled shape of z [%d,%d,%d,%d,%d]", who, dp->B, dp->T, dp->H, dp->W, dp->C, z->B,
+               z->T, z->H, z->W, z->C);
+  VN_CHECK_ARG(z->C <= 2048, "%s: C=%d is more than the 256 groups of one workgroup", who, z->C);
+  VN_CHECK_ARG(view_voxels(*z) < (1L << 31), "%s: too many voxels for 32-bit block indices", who);
+  return 0;
+}
+extern "C" int vinet_bn_bwd_pool_ok(const VinetPoolDesc* pool, const VinetTensor* z, const VinetTensor* dp, const VinetTensor* dx,
+                                    int32_t dtype) {
+  return bn_bwd_pool_args("bn_bwd_pool_ok", pool, z, dp, dx, dtype) == 0 ? 1 : 0;
+}
+
+extern "C" int vinet_bn_bwd_reduce_pool(const VinetPoolDesc* pool, const VinetTensor* dp, const uint8_t* argmax, const VinetTensor* gacc,
+                                        int32_t accumulate, const VinetTensor* z, int32_t dtype, VinetAffine fwd, const float* mean,
+                                        const float* invstd, float* partials, void* stream) {
+  VN_CHECK_ARG(gacc || !accumulate, "bn_bwd_reduce_pool: null argument");
+  if (bn_bwd_pool_args("bn_bwd_reduce_pool", pool, z, dp, gacc ? gacc : z, dtype)) return -1;
+  VN_CHECK_ARG(argmax && ((uintptr_t)argmax % 8) == 0 && mean && invstd && partials, "bn_bwd_reduce_pool: null or misaligned argument");
+  VN_CHECK_ARG((fwd.scale != nullptr) == (fwd.shift != nullptr), "bn_bwd_reduce_pool: a forward affine needs both its scale and its shift");
+  const int HB = (z->H + 1) / 2, WB = (z->W + 1) / 2;
+  const long nblk = (long)z->B * z->T * HB * WB;
+  const int rows = stats_rows_for(view_voxels(*z));
+  const long vb = g_vinet_opt_reduce_il ? 0 : (nblk + rows - 1) / rows;
+  const TView zv = make_view(*z), gv = make_view(accumulate ? *gacc : *z);
+  if (accumulate)
+    hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<true>, dim3(rows), dim3(256), 0, (hipStream_t)stream, zv, make_view(*dp), argmax, gv,
+                       make_affine(fwd), mean, invstd, make_fastdiv((uint32_t)WB), make_fastdiv((uint32_t)HB), nblk, vb, partials);
+  else
+    hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel<false>, dim3(rows), dim3(256), 0, (hipStream_t)stream, zv, make_view(*dp), argmax, gv,
+                       make_affine(fwd), mean, invstd, make_fastdiv((uint32_t)WB), make_fastdiv((uint32_t)HB), nblk, vb, partials);
+  return vn_launch_status("bn_bwd_reduce_pool");
+}
+
+extern "C" int vinet_bn_bwd_apply_pool(const VinetPoolDesc* pool, const VinetTensor* dp, const uint8_t* argmax, const VinetTensor* gacc,
+                                       int32_t accumulate, const VinetTensor* z, int32_t dtype, VinetAffine fwd, const float* mean,
+                                       const float* invstd, const float* c1, const float* c2, const VinetTensor* dx, void* stream) {
+  if (bn_bwd_pool_args("bn_bwd_apply_pool", pool, z, dp, dx, dtype)) return -1;
+  if (accumulate && bn_bwd_pool_args("bn_bwd_apply_pool", pool, z, dp, gacc, dtype)) return -1;
+  VN_CHECK_ARG(argmax && ((uintptr_t)argmax % 8) == 0 && fwd.scale && fwd.shift && mean && invstd && c1 && c2,
+               "bn_bwd_apply_pool: null or misaligned argument");
+  const int HB = (z->H + 1) / 2, WB = (z->W + 1) / 2;
+  const long nblk = (long)z->B * z->T * HB * WB;
+  const int G = z->C / 8, R = 256 / G;
+  long vb = R * 4;                                     // 4 blocks (16 voxels) per lane
+  while ((nblk + vb - 1) / vb > 16384) vb *= 2;
+  const dim3 grid((unsigned)((nblk + vb - 1) / vb));
+  const TView zv = make_view(*z), gv = make_view(accumulate ? *gacc : *dx);
+  if (accumulate)
+    hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, zv, make_view(*dp), argmax, gv,
+                       make_affine(fwd), mean, invstd, c1, c2, make_view(*dx), make_fastdiv((uint32_t)WB), make_fastdiv((uint32_t)HB), nblk, vb);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_pool_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, zv, make_view(*dp), argmax, gv,
+                       make_affine(fwd), mean, invstd, c1, c2, make_view(*dx), make_fastdiv((uint32_t)WB), make_fastdiv((uint32_t)HB), nblk, vb);
+  return vn_launch_status("bn_bwd_apply_pool");
 }
 
 template <typename TG, typename TZ, typename TO>

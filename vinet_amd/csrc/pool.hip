@@ -1,7 +1,7 @@
 // MaxPool3d forward / backward kernels (model.py:696-714, model_utils.py:178): generic gathers, the packed-key 8-channel
 // forward, LDS halo-tile and T-walking 3x3x3/s1 kernels, the 2x2-block 1x3x3/s2 backward.  The entry points are at the end
 // of the file: pool_fwd_route / pool_bwd_route decide the kernel, the launch and the name query read the same answer.
-#include "elementwise.h"
+#include "pool_gather.h"
 
 // ============================================================================
 // MaxPool3d
@@ -561,23 +561,6 @@ __global__ __launch_bounds__(512) void maxpool_k3s1_pk_kernel(TView x, Affine pr
   }
 }
 
-// g += v in the lanes whose code byte (byte BYTE of `word`) equals `code`: v_cmpx (SDWA byte select) -> add under EXEC -> EXEC restored
-#define POOL_ADD_IF_X(g, word, BYTE, code, v, exec0)                                                                                  \
-  asm volatile("v_cmpx_eq_u32_sdwa vcc, %1, %2 src0_sel:BYTE_" #BYTE " src1_sel:DWORD\n\tv_add_f32_e32 %0, %0, %3\n\ts_mov_b64 exec, %4" \
-               : "+v"(g) : "v"(word), "s"(code), "v"(v), "s"(exec0) : "vcc")
-#define POOL_ADD_IF(g, word, BYTE, code, v) POOL_ADD_IF_X(g, word, BYTE, code, v, exec0)
-// byte e (0..7) of a 64-bit code word
-#define POOL_ADD_IF8(g, lo, hi, e, code, v, ex)                                           \
-  do {                                                                                      \
-    const uint32_t w_ = (e) < 4 ? (lo) : (hi);                                              \
-    switch ((e) & 3) {                                                                      \
-      case 0: POOL_ADD_IF_X(g, w_, 0, code, v, ex); break;                                  \
-      case 1: POOL_ADD_IF_X(g, w_, 1, code, v, ex); break;                                  \
-      case 2: POOL_ADD_IF_X(g, w_, 2, code, v, ex); break;                                  \
-      default: POOL_ADD_IF_X(g, w_, 3, code, v, ex); break;                                 \
-    }                                                                                       \
-  } while (0)
-
 // backward as a gather over the (at most ceil(k/s)^3) windows covering each input voxel
 template <typename T>
 __global__ void maxpool_bwd_kernel(PoolP p, TView dy, const uint8_t* __restrict__ argmax, TView dx, int accumulate,
@@ -752,28 +735,12 @@ __global__ __launch_bounds__(256) void maxpool_bwd_k133s2_kernel(TView dy, const
   // windows q = dh*2 + dw at (hb + dh, wb + dw)
   unsigned long long am[4];
   bool wok[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int ho = hb + (q >> 1), wo = wb + (q & 1);
-    wok[q] = ho < dy.H && wo < dy.W;
-    const long ovox = (((long)b * dy.T + t) * dy.H + (wok[q] ? ho : 0)) * dy.W + (wok[q] ? wo : 0);
-    am[q] = wok[q] ? *(const unsigned long long*)(argmax + ovox * dy.C + g * 8) : ~0ull;
-  }
+  pool_k133s2_codes(dy, argmax, b, t, hb, wb, g, am, wok);
   float dv[4][8];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    // taps of window q that land in the block: rows kh in {1,2} (dh = 0) or {0} (dh = 1); same for columns
-    bool any = false;
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const bool in = ((q >> 1) ? kh == 0 : kh >= 1) && ((q & 1) ? kw == 0 : kw >= 1);
-        if (!in) continue;
-        const unsigned long long x = am[q] ^ ((unsigned long long)(kh * 3 + kw) * 0x0101010101010101ull);
-        any |= ((x - 0x0101010101010101ull) & ~x & 0x8080808080808080ull) != 0;
-      }
-    if (any) ld8<T>((const T*)dy.p + vox_off(dy, b, t, hb + (q >> 1), wb + (q & 1)) + g * 8, dv[q]);
+    // (a window none of whose taps lands in the block is not loaded)
+    if (pool_k133s2_any(am[q], q)) ld8<T>((const T*)dy.p + vox_off(dy, b, t, hb + (q >> 1), wb + (q & 1)) + g * 8, dv[q]);
     else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) dv[q][e] = 0.f;
@@ -788,16 +755,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_k133s2_kernel(TView dy, const
       float gr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       unsigned long long ex;                                  // (the lanes that are inside the image: POOL_ADD_IF restores this mask)
       asm volatile("s_mov_b64 %0, exec" : "=s"(ex));
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int dh = q >> 1, dw = q & 1;
-        // input (h, w) as tap (kh, kw) of window (hb + dh, wb + dw): kh = h + 1 - 2*(hb + dh) = ih + 1 - 2*dh
-        const int kh = ih + 1 - 2 * dh, kw = iw + 1 - 2 * dw;
-        if (kh < 0 || kw < 0) continue;                       // (compile-time: the window does not reach this input)
-        const uint32_t alo = (uint32_t)am[q], ahi = (uint32_t)(am[q] >> 32);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) POOL_ADD_IF8(gr[e], alo, ahi, e, (uint32_t)(kh * 3 + kw), dv[q][e], ex);
-      }
+      pool_k133s2_sum(am, dv, ih, iw, ex, gr);
       T* dst = (T*)dx.p + vox_off(dx, b, t, h, w) + g * 8;
       if (accumulate) {
         float o[8];

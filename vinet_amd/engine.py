@@ -100,6 +100,7 @@ _CONFIG = dict(
     # an issue-bound epilogue): 282.8 -> 286.7 ms per step in alternating same-box runs (profiles/r5_bnb_epilogue_ab.txt)
     DGRAD_BN_STATS=1,
     UPSAMPLE_BWD_RELU=1,        # ReLU backward of conv -> ReLU -> upsample inside the upsample's backward pass
+    POOL_BWD_IN_BN=1,           # 1x3x3/s2 pool backward formed inside the BN backward behind it: 274.4 -> 269.5 ms per step (profiles/pool_in_bn_*)
     PARAM_GRAD_MODE="fused",    # see set_param_grad_mode
     # Schedule stress (tests): shader clocks a spin kernel idles on the weight-gradient stream in front of every weight-gradient
     # launch (DBG_SPIN_SIDE) / on the main stream in front of every data gradient (DBG_SPIN_MAIN) / on a branch stream each time
@@ -294,7 +295,8 @@ class View:
 class Act:
     """activation = view + pending affine/relu + gradient bookkeeping."""
     __slots__ = ("v", "scale", "shift", "relu", "_grad", "grad_ready", "needs_grad", "parent", "pc0", "pt0", "fold",
-                 "indep", "ready_of", "grad_marks", "mean", "invstd", "alias_of", "n_readers", "act_out", "grad_masked", "prows")
+                 "indep", "ready_of", "grad_marks", "mean", "invstd", "alias_of", "n_readers", "act_out", "grad_masked", "prows", "bn1",
+                 "pool_rec")
 
     def __init__(self, v, scale=None, shift=None, relu=False, needs_grad=False, mean=None, invstd=None):
         self.v, self.scale, self.shift, self.relu = v, scale, shift, relu
@@ -312,6 +314,8 @@ class Act:
         self.act_out = 0         # activation the producing conv applied in its epilogue (no BatchNorm): conv_forward
         self.grad_masked = -1    # grad_marks at which the gradient already carries that activation's backward (upsample2x backward)
         self.prows = None        # (first row, T, H, W): a row range of the parent's positions under dims of its own (sub_rows)
+        self.bn1 = False         # relu(bn(z)) of ONE recorded training-mode BatchNorm (conv_forward; not a joint conv's)
+        self.pool_rec = None     # on the owner of gradient storage: a max-pool backward into it that has not run (_PoolRec)
 
     @property
     def plain(self):
@@ -373,6 +377,9 @@ class Act:
             if self.pt0 is None:
                 return g.chan(self.pc0, self.pc0 + self.v.C)
             return g.tslice(self.pt0, self.pt0 + self.v.T)
+        if self.pool_rec is not None:
+            # somebody other than the BatchNorm backward the deferred pool backward waits for wants this gradient: it runs now
+            self.pool_rec.flush(self)
         if self._grad is None:
             v = self.v
             self._grad = View.alloc(v.B, v.T, v.H, v.W, v.C, v.dt if dt is None else dt, v.device, zero=zero)
@@ -389,6 +396,39 @@ class Act:
         r = self.root()
         r.grad_ready = True
         r.grad_marks += 1
+
+
+class _PoolRec:
+    """a 1x3x3/s2 max-pool backward that did NOT run (maxpool_forward, POOL_BWD_IN_BN): the pool was the last writer of the gradient
+    of x = relu(bn(z)), so the BatchNorm backward of x's producer forms that gradient in registers from (dp, argmax, what the
+    buffer holds) -- _bn_backward.  The record sits on the Act that owns the gradient STORAGE: every access to that storage, through
+    any slice or alias, passes its grad_view(), which runs the ordinary pool backward first unless _take_pool_rec got there before."""
+    __slots__ = ("x", "pd", "dp", "am", "acc", "launch")
+
+    def __init__(self, x, pd, dp, am, acc, launch):
+        self.x, self.pd, self.dp, self.am, self.acc, self.launch = x, pd, dp, am, acc, launch
+
+    def flush(self, owner):
+        owner.pool_rec = None        # (first: the launch asks for the gradient view itself)
+        self.launch(self.acc)
+
+
+def _grad_owner(a):
+    """the Act that owns the gradient storage of `a`"""
+    while a.parent is not None:
+        a = a.parent
+    return a
+
+
+def _take_pool_rec(res, bn, train_bn, x):
+    """the deferred pool backward into the gradient of `res`, for the BatchNorm backward of res's producer to fold in; None (and the
+    record, if any, stays: res.grad_view() will run it) unless it is exactly this layer's"""
+    owner = _grad_owner(res)
+    rec = owner.pool_rec
+    if rec is None or rec.x is not res or bn is None or isinstance(bn, JointBN) or not train_bn or not x.needs_grad:
+        return None
+    owner.pool_rec = None
+    return rec
 
 
 def _abs_chan(a):
@@ -1283,6 +1323,7 @@ def conv_forward(ctx, plan, x, bn=None, act=L.ACT_NONE, dst=None, out_dt=None, n
         res.scale, res.shift, res.relu = scale, shift, (act == L.ACT_RELU)
         keep.update(mean=mean, invstd=invstd)
         res.mean, res.invstd = mean, invstd      # (a consumer's data gradient may fold this BatchNorm's backward reduce pass in: _data_grad)
+        res.bn1 = not isinstance(bn, JointBN)
     else:
         scale, shift = (ctx.f32(plan.N) if g is None else g for g in given[:2])
         if ctx.recording:
@@ -1397,11 +1438,12 @@ def _wgrad_desc(ctx, plan, x, dy, dw=None):
 
 def _conv_backward(ctx, plan, x, res, bn, act, train_bn, keep, M):
     """backward of one conv_forward in four stages: dz -> dy through BatchNorm / activation, bias, weight and data gradient"""
+    pool = _take_pool_rec(res, bn, train_bn, x)      # (before the gradient is asked for: that would run the deferred pool backward)
     dz = res.grad_view()
     assert res.is_grad_ready(), "conv backward reached before any consumer produced a gradient"
     fused_bnb = dy_planes = None
     if bn is not None:
-        dy, fused_bnb, dy_planes = _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz)
+        dy, fused_bnb, dy_planes = _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz, pool)
     else:
         dy = _act_backward(ctx, res, act, dz)
     if plan.bias is not None and plan.bias.requires_grad:
@@ -1414,7 +1456,7 @@ def _conv_backward(ctx, plan, x, res, bn, act, train_bn, keep, M):
         _data_grad(ctx, plan, x, res.v, dy, M)
 
 
-def _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz):
+def _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz, pool=None):
     """stage 1 behind a BatchNorm: dz (w.r.t. the BN + ReLU output) -> dy (w.r.t. the raw conv output), in place.  Returns
     (dy, fused, planes): `fused` = (z, forward affine, mean, invstd, c1, c2) when the weight-gradient kernel forms dy on the fly
     and no apply pass ran (else None); `planes` = the fp32s (hi, lo) bf16 planes of dy the apply pass wrote (else None)"""
@@ -1422,6 +1464,21 @@ def _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz):
     fwd = res.affine()
     mean, invstd = keep["mean"], keep["invstd"]
     nb = float(dz.nvox * dz.C * ESIZE[dz.dt])
+    if pool is not None:
+        # dz does not exist: the last writer of this gradient, a 1x3x3/s2 max-pool backward, was deferred (_PoolRec).  Both passes
+        # form it from (dp, argmax, the buffer's contents when accumulating); the apply pass writes dy where dz would have been.
+        nq = float(pool.dp.nvox * dz.C)                      # dp (2 bytes) and the argmax codes (1) per pooled element
+        rows = ctx.lib.vinet_stats_rows(C.byref(out.ct()))
+        ws = ctx.f32(rows * 2 * Ny)
+        c1, c2 = ctx.f32(Ny), ctx.f32(Ny)
+        ctx.call("vinet_bn_bwd_reduce_pool", C.byref(pool.pd), C.byref(pool.dp.ct()), pool.am.data_ptr(), C.byref(dz.ct()), pool.acc,
+                 C.byref(out.ct()), dz.dt, fwd, mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ctx.stream,
+                 tag=_bn_tag("reduce", Ny, dz, " pool"), work=dict(flops=0.0, bytes=(1 + pool.acc) * nb + 3 * nq))
+        bn.bwd_finalize(ctx, ws, rows, Ny, M, res.scale, train_bn, invstd, c1, c2, off=0, ld=Ny, ws_off=0)
+        ctx.call("vinet_bn_bwd_apply_pool", C.byref(pool.pd), C.byref(pool.dp.ct()), pool.am.data_ptr(), C.byref(dz.ct()), pool.acc,
+                 C.byref(out.ct()), dz.dt, fwd, mean.data_ptr(), invstd.data_ptr(), c1.data_ptr(), c2.data_ptr(), C.byref(dz.ct()),
+                 ctx.stream, tag=_bn_tag("apply", Ny, dz, " pool"), work=dict(flops=0.0, bytes=(2 + pool.acc) * nb + 3 * nq))
+        return dz, None, None
     # per BatchNorm behind this conv (one, or the members of a joint entry conv): its two backward sums either came with the
     # gradient -- the data gradient that wrote dz LAST left their partial rows (VinetConvDesc::bnb_*; _find_bnb checks that
     # no writer came after it) -- or need a reduce pass over (dz, z)
@@ -1469,8 +1526,8 @@ def _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz):
     return dz, None, None
 
 
-def _bn_tag(what, width, dz):
-    return ("vinet_bn_bwd_%s | C%d x %d voxels" % (what, width, dz.nvox)) if PROFILER is not None else None
+def _bn_tag(what, width, dz, mark=""):
+    return ("vinet_bn_bwd_%s | C%d x %d voxels%s" % (what, width, dz.nvox, mark)) if PROFILER is not None else None
 
 
 def _act_backward(ctx, res, act, dz):
@@ -1684,15 +1741,46 @@ def maxpool_forward(ctx, x, k, s, p, dst=None):
              tag="maxpool_fwd_kernel | " + ptag, work=dict(flops=0.0, bytes=float((xv.nvox + out.nvox) * xv.C * es)))
     dst.needs_grad = x.needs_grad
     if rec:
-        def bwd():
+        def launch(acc):
             dy = dst.grad_view()
             dx = x.grad_view()
             ctx.call("vinet_maxpool3d_bwd", C.byref(pd), C.byref(dy.ct()), am.data_ptr(), C.byref(dx.ct()),
-                     1 if x.is_grad_ready() else 0, ctx.stream, tag="maxpool_bwd_kernel | " + ptag,
+                     acc, ctx.stream, tag="maxpool_bwd_kernel | " + ptag,
                      work=dict(flops=0.0, bytes=float((xv.nvox + out.nvox) * xv.C * es + out.nvox * xv.C)))
+
+        def bwd():
+            acc = 1 if x.is_grad_ready() else 0
+            if _pool_bwd_defers(ctx, x, pd, k, s, p):
+                dy, dx = dst.grad_view(), x.grad_view()
+                if dy.dt == dx.dt == BF16 and ctx.lib.vinet_bn_bwd_pool_ok(C.byref(pd), C.byref(xv.ct()), C.byref(dy.ct()),
+                                                                          C.byref(dx.ct()), xv.dt):
+                    # the BatchNorm backward of x's producer forms this gradient itself (_bn_backward); anybody else who asks for
+                    # it first gets the ordinary launch (Act.grad_view)
+                    _grad_owner(x).pool_rec = _PoolRec(x, pd, dy, am, acc, launch)
+                    x.mark_grad_ready()
+                    return
+            launch(acc)
             x.mark_grad_ready()
         ctx.record(bwd)
     return dst
+
+
+def _pool_bwd_defers(ctx, x, pd, k, s, p):
+    """may this pool backward be left to the BatchNorm backward behind x?  x = relu(bn(z)) of one recorded training-mode BatchNorm,
+    bf16 arithmetic, the 1x3x3 / s(1,2,2) / p(0,1,1) pool, a library with the fused kernels -- and the pool is the LAST writer of
+    x's gradient: every other consumer recorded in forward has written.  A gradient that lives in a decoder concat's (materialize,
+    share_grad) counts the concat's consumers and, the sharing one apart, x's own."""
+    if not (POOL_BWD_IN_BN and x.bn1 and x.relu and x.scale is not None and x.mean is not None and x.fold is None and x.prows is None
+            and x.alias_of is None and ctx.cdt == BF16 and x.v.dt == BF16 and (k, s, p) == ((1, 3, 3), (1, 2, 2), (0, 1, 1))
+            and getattr(ctx.lib, "vinet_bn_bwd_pool_ok", None) is not None and hasattr(ctx.lib, "vinet_bn_bwd_reduce_pool")
+            and hasattr(ctx.lib, "vinet_bn_bwd_apply_pool")):
+        return False
+    r = x.root()
+    if r is x:
+        return x.parent is None and r.grad_marks + 1 == r.n_readers
+    if x.indep or x.pc0 != 0 or x.pt0 is not None or x.parent.v.C != x.v.C:
+        return False            # (a concat member: other layers write into the same root)
+    return r.grad_marks + 1 == r.n_readers + x.n_readers - 1
 
 
 def upsample2x_forward(ctx, x, dst=None):
