@@ -373,6 +373,20 @@ int vinet_maxpool3d_kernel_name(const VinetPoolDesc* d, const VinetTensor* x, Vi
                                 const uint8_t* argmax, char* buf, int32_t n);
 int vinet_maxpool3d_bwd_kernel_name(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax,
                                     const VinetTensor* dx, char* buf, int32_t n);
+/* vinet_maxpool3d that ALSO stores pre(x), rounded to bf16, to the view `keep`: x's B/T/H/W/C with any ld / sB / base pointer (a T
+ * slice of a longer buffer, a channel slice).  y and argmax are bit-identical to vinet_maxpool3d's; `keep` holds what
+ * vinet_copy_affine(x, pre) would have written, up to the sign of a zero behind a ReLU (integer max after rounding, not fmaxf before
+ * it).  Each lane stores the window taps with index in [p, p + s) of every dimension, so no element is loaded or transformed twice.
+ * Served: bf16, the route maxpool_fwd8_pk_kernel (the default for every bf16 window but 3x3x3/s1/p1 on 8-channel views), `keep` in
+ * whole groups of 8 channels on 16-byte addresses, and in every dimension k >= p + s and out * s >= in, so that the owned taps tile
+ * the input: 1x3x3/s(1,2,2)/p(0,1,1), 3x3x3/s2/p1, (2,1,1)/s(2,1,1) at even T, (1,2,2)/s(1,2,2) at even H and W.  Not served: fp32,
+ * the LDS / T-walking 3x3x3/s1 kernels, the 4-channel kernels, lib option pool_pk = 0, a stride that leaves input uncovered (odd T
+ * under (2,1,1)/s2).  vinet_maxpool3d_keep_ok: 1 if this very call is served, else 0 with the reason in vinet_last_error; the entry
+ * point itself returns -1 on such a call and launches nothing. */
+int vinet_maxpool3d_keep_ok(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
+                            const uint8_t* argmax, const VinetTensor* keep);
+int vinet_maxpool3d_keep(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
+                         uint8_t* argmax, const VinetTensor* keep, void* stream);
 /* BatchNorm backward behind the 1x3x3 / s(1,2,2) / p(0,1,1) pool, the pool's backward folded in: the gradient dz behind
  * relu(bn(z)) is never stored.  Both passes form it in registers exactly as vinet_maxpool3d_bwd(pool, dp, argmax, gacc, accumulate)
  * would have stored it (bf16, + the old contents of `gacc` when `accumulate`) and continue as vinet_bn_bwd_reduce /

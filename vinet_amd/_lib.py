@@ -108,6 +108,8 @@ SIGNATURES = {
     "vinet_channel_sum": [_PT, _i32, _vp, _i32, _vp, _i32, _vp],
     "vinet_maxpool3d": [_PP, _PT, CAffine, _PT, _vp, _vp],
     "vinet_maxpool3d_bwd": [_PP, _PT, _vp, _PT, _i32, _vp],
+    "vinet_maxpool3d_keep_ok": [_PP, _PT, CAffine, _PT, _vp, _PT],
+    "vinet_maxpool3d_keep": [_PP, _PT, CAffine, _PT, _vp, _PT, _vp],
     "vinet_maxpool3d_kernel_name": [_PP, _PT, CAffine, _PT, _vp, C.c_char_p, _i32],
     "vinet_maxpool3d_bwd_kernel_name": [_PP, _PT, _vp, _PT, C.c_char_p, _i32],
     "vinet_upsample2x": [_PT, _PT, _i32, _vp],

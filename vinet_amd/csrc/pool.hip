@@ -393,7 +393,15 @@ VN_DEV uint32_t pool_decode2(uint32_t k) {
 // Generic window (any k / stride / padding, up to 255 taps), bf16, on packed keys: one lane = one output voxel x 8
 // channels; every in-range tap is loaded (16 B), transformed, coded and folded with key = code << 16 | (ntaps-1-tap).
 // 7 VALU per element and tap instead of ~12 for affine + round + compare-and-track in fp32.
-__global__ __launch_bounds__(256) void maxpool_fwd8_pk_kernel(PoolP p, TView x, Affine pre, TView y, uint8_t* __restrict__ argmax, long total) {
+// KEEP (maxpool_fwd8_pk_keep_kernel, vinet_maxpool3d_keep): the lane also stores the transformed, bf16-rounded taps it OWNS -- tap
+// index in [p, p + s) of every dimension, i.e. the input block [o * s, o * s + s) of its output voxel -- to the view `keep` (x's
+// dims, strides of its own).
+// pool_keep_args admits only windows with k >= p + s and out * s >= in in every dimension: the owned blocks then tile the input, so
+// every element of `keep` is written exactly once, from a value the lane holds anyway (no extra load, one compare chain per tap).
+// Non-temporal stores: `keep` is read again a whole encoder later, and the input rows that neighbouring windows share stay in L2.
+template <bool KEEP>
+VN_DEV void maxpool_fwd8_pk_lane(const PoolP& p, const TView& x, const Affine& pre, const TView& y, uint8_t* __restrict__ argmax, long total,
+                                 const TView& keep) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int G = y.C >> 3;
@@ -437,6 +445,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd8_pk_kernel(PoolP p, TView x, 
           best[2 * e] = best[2 * e] > klo ? best[2 * e] : klo;
           best[2 * e + 1] = best[2 * e + 1] > khi ? best[2 * e + 1] : khi;
         }
+        if (KEEP && (unsigned)(kt - p.pT) < (unsigned)p.sT && (unsigned)(kh - p.pH) < (unsigned)p.sH && (unsigned)(kw - p.pW) < (unsigned)p.sW)
+          st16_nt((bf16_t*)keep.p + vox_off(keep, b, t, h, w) + g * 8, make_uint4(w4[0], w4[1], w4[2], w4[3]));
       }
     }
   }
@@ -452,6 +462,13 @@ __global__ __launch_bounds__(256) void maxpool_fwd8_pk_kernel(PoolP p, TView x, 
   o.x = pool_decode2(ov[0]); o.y = pool_decode2(ov[1]); o.z = pool_decode2(ov[2]); o.w = pool_decode2(ov[3]);
   *(uint4*)((bf16_t*)y.p + vox_off(y, b, to, ho, wo) + g * 8) = o;
   if (argmax) *(unsigned long long*)(argmax + (long)vox_u * y.C + g * 8) = bi;
+}
+__global__ __launch_bounds__(256) void maxpool_fwd8_pk_kernel(PoolP p, TView x, Affine pre, TView y, uint8_t* __restrict__ argmax, long total) {
+  maxpool_fwd8_pk_lane<false>(p, x, pre, y, argmax, total, x);
+}
+__global__ __launch_bounds__(256) void maxpool_fwd8_pk_keep_kernel(PoolP p, TView x, Affine pre, TView y, uint8_t* __restrict__ argmax,
+                                                                   long total, TView keep) {
+  maxpool_fwd8_pk_lane<true>(p, x, pre, y, argmax, total, keep);
 }
 
 // bf16 form of the kernel above on PACKED 32-bit keys.  The halo holds order-preserving 16-bit codes of the
@@ -1112,6 +1129,40 @@ extern "C" int vinet_maxpool3d(const VinetPoolDesc* d, const VinetTensor* x, Vin
     default: break;      // (the backward's kinds: pool_fwd_route never answers them)
   }
   return vn_launch_status(r.name);
+}
+
+// what vinet_maxpool3d_keep serves: bf16 on maxpool_fwd8_pk_kernel (never the LDS / T-walking 3x3x3/s1 kernels, never fp32), `keep`
+// of x's dims on the 16-byte, 8-channel grid, and a window whose owned taps [p, p + s) exist (k >= p + s) and whose owned blocks
+// reach the end of the input (out * s >= in) in every dimension
+static int pool_keep_args(const char* who, const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
+                          const uint8_t* argmax, const VinetTensor* keep) {
+  if (pool_fwd_args(d, x, pre, y)) return -1;
+  VN_CHECK_ARG(keep, "%s: null argument", who);
+  VN_CHECK_ARG(d->dtype == VINET_BF16, "%s: bf16 only (pool dtype %d)", who, d->dtype);
+  VN_CHECK_ARG(d->sT > 0 && d->sH > 0 && d->sW > 0 && d->pT >= 0 && d->pH >= 0 && d->pW >= 0, "%s: bad stride or padding", who);
+  VN_CHECK_ARG(pool_fwd_route(d, x, y, argmax).kind == POOL_FWD8_PK, "%s: the pool runs on %s, not on maxpool_fwd8_pk_kernel", who,
+               pool_fwd_route(d, x, y, argmax).name);
+  VN_CHECK_ARG(oct_ok(*keep) && same_dims(*keep, *x), "%s: keep is off the 16-byte, 8-channel grid or differs from x in its dims", who);
+  VN_CHECK_ARG(d->kT >= d->pT + d->sT && d->kH >= d->pH + d->sH && d->kW >= d->pW + d->sW,
+               "%s: window %dx%dx%d / s(%d,%d,%d) / p(%d,%d,%d) lacks the taps [p, p + s) that own the input", who, d->kT, d->kH, d->kW,
+               d->sT, d->sH, d->sW, d->pT, d->pH, d->pW);
+  VN_CHECK_ARG((long)y->T * d->sT >= x->T && (long)y->H * d->sH >= x->H && (long)y->W * d->sW >= x->W,
+               "%s: outputs [%d,%d,%d] x strides (%d,%d,%d) do not cover the input [%d,%d,%d]", who, y->T, y->H, y->W, d->sT, d->sH, d->sW,
+               x->T, x->H, x->W);
+  return 0;
+}
+extern "C" int vinet_maxpool3d_keep_ok(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
+                                       const uint8_t* argmax, const VinetTensor* keep) {
+  return pool_keep_args("maxpool3d_keep_ok", d, x, pre, y, argmax, keep) == 0 ? 1 : 0;
+}
+extern "C" int vinet_maxpool3d_keep(const VinetPoolDesc* d, const VinetTensor* x, VinetAffine pre, const VinetTensor* y,
+                                    uint8_t* argmax, const VinetTensor* keep, void* stream) {
+  if (pool_keep_args("maxpool3d_keep", d, x, pre, y, argmax, keep)) return -1;
+  const PoolRoute r = pool_fwd_route(d, x, y, argmax);
+  // (the kernel in parentheses: no route of vinet_maxpool3d names it, and tests/test_route_tables.py reads those off the launch sites)
+  hipLaunchKernelGGL((maxpool_fwd8_pk_keep_kernel), dim3(ew_grid(r.n)), dim3(256), 0, (hipStream_t)stream, make_poolp(d), make_view(*x),
+                     make_affine(pre), make_view(*y), argmax, r.n, make_view(*keep));
+  return vn_launch_status("maxpool_fwd8_pk_keep_kernel");
 }
 
 extern "C" int vinet_maxpool3d_bwd(const VinetPoolDesc* d, const VinetTensor* dy, const uint8_t* argmax,

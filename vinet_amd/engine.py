@@ -101,6 +101,10 @@ _CONFIG = dict(
     DGRAD_BN_STATS=1,
     UPSAMPLE_BWD_RELU=1,        # ReLU backward of conv -> ReLU -> upsample inside the upsample's backward pass
     POOL_BWD_IN_BN=1,           # 1x3x3/s2 pool backward formed inside the BN backward behind it: 274.4 -> 269.5 ms per step (profiles/pool_in_bn_*)
+    # the max-pool behind a decoder skip also writes relu(bn(skip)) into the skip's slice of the decoder's T-concat (vinet_maxpool3d_keep):
+    # the three vinet_copy_affine passes of the skips (11.2 GB read at 192 clips) never run: 269.2 -> 266.4 ms per step
+    # (profiles/pool_keep_*).  0 = the copies.
+    POOL_KEEPS_SKIP=1,
     PARAM_GRAD_MODE="fused",    # see set_param_grad_mode
     # Schedule stress (tests): shader clocks a spin kernel idles on the weight-gradient stream in front of every weight-gradient
     # launch (DBG_SPIN_SIDE) / on the main stream in front of every data gradient (DBG_SPIN_MAIN) / on a branch stream each time
@@ -296,7 +300,7 @@ class Act:
     """activation = view + pending affine/relu + gradient bookkeeping."""
     __slots__ = ("v", "scale", "shift", "relu", "_grad", "grad_ready", "needs_grad", "parent", "pc0", "pt0", "fold",
                  "indep", "ready_of", "grad_marks", "mean", "invstd", "alias_of", "n_readers", "act_out", "grad_masked", "prows", "bn1",
-                 "pool_rec")
+                 "pool_rec", "kept_in")
 
     def __init__(self, v, scale=None, shift=None, relu=False, needs_grad=False, mean=None, invstd=None):
         self.v, self.scale, self.shift, self.relu = v, scale, shift, relu
@@ -316,6 +320,7 @@ class Act:
         self.prows = None        # (first row, T, H, W): a row range of the parent's positions under dims of its own (sub_rows)
         self.bn1 = False         # relu(bn(z)) of ONE recorded training-mode BatchNorm (conv_forward; not a joint conv's)
         self.pool_rec = None     # on the owner of gradient storage: a max-pool backward into it that has not run (_PoolRec)
+        self.kept_in = None      # the View that already holds this activation's materialised values (maxpool_forward, keep=)
 
     @property
     def plain(self):
@@ -744,7 +749,8 @@ def materialize(ctx, a, dst=None, out_dt=None, share_grad=False):
         dst = Act(View.alloc(v.B, v.T, v.H, v.W, v.C, dt, v.device))
     out = dst.v
     assert out.same_dims(v) and dst.plain
-    ctx.call("vinet_copy_affine", C.byref(v.ct()), v.dt, a.affine(), C.byref(out.ct()), out.dt, 0, ctx.stream)
+    if not _same_view(a.kept_in, out):       # (else: the max-pool that read `a` has written these very values there)
+        ctx.call("vinet_copy_affine", C.byref(v.ct()), v.dt, a.affine(), C.byref(out.ct()), out.dt, 0, ctx.stream)
     dst.needs_grad = a.needs_grad
     if alias:
         dst.parent, dst.pc0, dst.pt0 = a, 0, None        # identity "slice": grad_view / readiness resolve into a's
@@ -764,6 +770,11 @@ def materialize(ctx, a, dst=None, out_dt=None, share_grad=False):
             a.mark_grad_ready()
         ctx.record(bwd)
     return dst
+
+
+def _same_view(a, b):
+    return a is not None and a.buf is b.buf and a.dt == b.dt and \
+        (a.off, a.B, a.T, a.H, a.W, a.C, a.ld, a.sB) == (b.off, b.B, b.T, b.H, b.W, b.C, b.ld, b.sB)
 
 
 def new_concat(ctx, B, T, H, W, Ctot, pending):
@@ -1724,7 +1735,16 @@ def _data_grad(ctx, plan, x, out, dy, M):
 # pooling / upsample
 # ----------------------------------------------------------------------------
 
-def maxpool_forward(ctx, x, k, s, p, dst=None):
+def pool_keeps_skip(ctx):
+    """do the pools behind the decoder skips write the skips' materialised values themselves (maxpool_forward, keep=)?"""
+    return bool(POOL_KEEPS_SKIP) and ctx.dt == BF16 and getattr(ctx.lib, "vinet_maxpool3d_keep_ok", None) is not None \
+        and hasattr(ctx.lib, "vinet_maxpool3d_keep")
+
+
+def maxpool_forward(ctx, x, k, s, p, dst=None, keep=None):
+    """keep: a plain Act of x's extent (a slice of a decoder concat) that is to hold x's materialised values; where the library
+    can, the pool writes them on its way (vinet_maxpool3d_keep) and x remembers the view, so that materialize(x, keep) launches
+    nothing.  Where it cannot, nothing changes: that materialize copies."""
     xv = x.v
     od = tuple((d + 2 * pp - kk) // ss + 1 for d, kk, ss, pp in zip((xv.T, xv.H, xv.W), k, s, p))
     if dst is None:
@@ -1737,8 +1757,18 @@ def maxpool_forward(ctx, x, k, s, p, dst=None):
     am = torch.empty(out.nvox * out.C, dtype=torch.uint8, device=xv.device) if rec else None
     ptag = "maxpool k%dx%dx%d s%dx%dx%d C%d in%dx%dx%dx%d" % (k + s + (xv.C, xv.B, xv.T, xv.H, xv.W))
     es = ESIZE[xv.dt]
-    ctx.call("vinet_maxpool3d", C.byref(pd), C.byref(xv.ct()), x.affine(), C.byref(out.ct()), _ptr(am), ctx.stream,
-             tag="maxpool_fwd_kernel | " + ptag, work=dict(flops=0.0, bytes=float((xv.nvox + out.nvox) * xv.C * es)))
+    kv = keep.v if keep is not None and pool_keeps_skip(ctx) and keep.plain and keep.v.dt == xv.dt and keep.v.same_dims(xv) else None
+    if kv is not None and not ctx.lib.vinet_maxpool3d_keep_ok(C.byref(pd), C.byref(xv.ct()), x.affine(), C.byref(out.ct()), _ptr(am),
+                                                              C.byref(kv.ct())):
+        kv = None
+    if kv is not None:
+        ctx.call("vinet_maxpool3d_keep", C.byref(pd), C.byref(xv.ct()), x.affine(), C.byref(out.ct()), _ptr(am), C.byref(kv.ct()),
+                 ctx.stream, tag="maxpool_fwd_kernel | " + ptag + " +keep",
+                 work=dict(flops=0.0, bytes=float((2 * xv.nvox + out.nvox) * xv.C * es)))
+        x.kept_in = kv
+    else:
+        ctx.call("vinet_maxpool3d", C.byref(pd), C.byref(xv.ct()), x.affine(), C.byref(out.ct()), _ptr(am), ctx.stream,
+                 tag="maxpool_fwd_kernel | " + ptag, work=dict(flops=0.0, bytes=float((xv.nvox + out.nvox) * xv.C * es)))
     dst.needs_grad = x.needs_grad
     if rec:
         def launch(acc):

@@ -14,12 +14,28 @@ from torch import nn
 
 from . import _lib as L
 from . import engine as E
-from .model_utils import (BasicConv3d, BNParams2d, ConvParams, Mixed_3b, Mixed_3c, Mixed_4b, Mixed_4c, Mixed_4d,
+from .model_utils import (MIXED_WIDTHS, BasicConv3d, BNParams2d, ConvParams, Mixed_3b, Mixed_3c, Mixed_4b, Mixed_4c, Mixed_4d,
                           Mixed_4e, Mixed_4f, Mixed_5b, Mixed_5c, SepConv3d, _Block, _Marker)
 
 
 def _pool_marker(k, s, p):
     return _Marker("maxpool3d", kernel_size=k, stride=s, padding=p)
+
+
+def _window_dims(dims, k, s, p):
+    """nn.Conv3d / nn.MaxPool3d extent arithmetic"""
+    return tuple((d + 2 * pp - kk) // ss + 1 for d, kk, ss, pp in zip(dims, k, s, p))
+
+
+def _sep_dims(sep, dims):
+    for conv in (sep.conv_s, sep.conv_t):
+        dims = _window_dims(dims, conv.kernel_size, conv.stride, conv.padding)
+    return dims
+
+
+# the five pools of BackBoneS3D (model.py:696,700,705,713,714)
+POOL_1, POOL_2, POOL_3 = ((1, 3, 3), (1, 2, 2), (0, 1, 1)), ((1, 3, 3), (1, 2, 2), (0, 1, 1)), ((3, 3, 3), (2, 2, 2), (1, 1, 1))
+POOL_T4, POOL_P4 = ((2, 1, 1), (2, 1, 1), (0, 0, 0)), ((1, 2, 2), (1, 2, 2), (0, 0, 0))
 
 
 class BackBoneS3D(_Block):
@@ -30,31 +46,44 @@ class BackBoneS3D(_Block):
         super().__init__()
         self.base1 = nn.Sequential(
             SepConv3d(3, 64, kernel_size=7, stride=2, padding=3),
-            _pool_marker((1, 3, 3), (1, 2, 2), (0, 1, 1)),
+            _pool_marker(*POOL_1),
             BasicConv3d(64, 64, kernel_size=1, stride=1),
             SepConv3d(64, 192, kernel_size=3, stride=1, padding=1),
         )
-        self.maxp2 = _pool_marker((1, 3, 3), (1, 2, 2), (0, 1, 1))
+        self.maxp2 = _pool_marker(*POOL_2)
         self.base2 = nn.Sequential(Mixed_3b(), Mixed_3c())
-        self.maxp3 = _pool_marker((3, 3, 3), (2, 2, 2), (1, 1, 1))
+        self.maxp3 = _pool_marker(*POOL_3)
         self.base3 = nn.Sequential(Mixed_4b(), Mixed_4c(), Mixed_4d(), Mixed_4e(), Mixed_4f())
-        self.maxt4 = _pool_marker((2, 1, 1), (2, 1, 1), (0, 0, 0))
-        self.maxp4 = _pool_marker((1, 2, 2), (1, 2, 2), (0, 0, 0))
+        self.maxt4 = _pool_marker(*POOL_T4)
+        self.maxp4 = _pool_marker(*POOL_P4)
         self.base4 = nn.Sequential(Mixed_5b(), Mixed_5c())
 
-    def _fwd(self, ctx, x):
+    def feature_dims(self, T, H, W):
+        """(T, H, W, C) of [y0, y1, y2, y3] for a T x H x W clip, by the layers' own extent arithmetic (no launch)"""
+        d = _window_dims(_sep_dims(self.base1[0], (T, H, W)), *POOL_1)
+        d3 = _sep_dims(self.base1[3], d)                      # (base1[2] and the Inception stages keep their extent)
+        d2 = _window_dims(d3, *POOL_2)
+        d1 = _window_dims(d2, *POOL_3)
+        d0 = _window_dims(_window_dims(d1, *POOL_T4), *POOL_P4)
+        widths = [sum(MIXED_WIDTHS[n][i] for i in (1, 3, 5, 6)) for n in ("5c", "4f", "3c")]
+        return [d0 + (widths[0],), d1 + (widths[1],), d2 + (widths[2],), d3 + (self.base1[3].conv_t.out_channels,)]
+
+    def _fwd(self, ctx, x, keep=None):
+        """keep: (for y1, for y2, for y3) plain Acts -- the skips' slices of the decoder's T-concats -- that the pools behind the
+        skips fill with the skips' materialised values where they can (engine.maxpool_forward)"""
+        k1, k2, k3 = keep if keep is not None else (None, None, None)
         y = self.base1[0]._fwd(ctx, x)
-        y = E.maxpool_forward(ctx, y, (1, 3, 3), (1, 2, 2), (0, 1, 1))
+        y = E.maxpool_forward(ctx, y, *POOL_1)
         y = self.base1[2]._fwd(ctx, y)
         y3 = self.base1[3]._fwd(ctx, y)
-        y = E.maxpool_forward(ctx, y3, (1, 3, 3), (1, 2, 2), (0, 1, 1))
+        y = E.maxpool_forward(ctx, y3, *POOL_2, keep=k3)
         y2 = self.base2[1]._fwd(ctx, self.base2[0]._fwd(ctx, y))
-        y = E.maxpool_forward(ctx, y2, (3, 3, 3), (2, 2, 2), (1, 1, 1))
+        y = E.maxpool_forward(ctx, y2, *POOL_3, keep=k2)
         for blk in self.base3:
             y = blk._fwd(ctx, y)
         y1 = y
-        y = E.maxpool_forward(ctx, y1, (2, 1, 1), (2, 1, 1), (0, 0, 0))
-        y = E.maxpool_forward(ctx, y, (1, 2, 2), (1, 2, 2), (0, 0, 0))
+        y = E.maxpool_forward(ctx, y1, *POOL_T4, keep=k1)
+        y = E.maxpool_forward(ctx, y, *POOL_P4)
         y0 = self.base4[1]._fwd(ctx, self.base4[0]._fwd(ctx, y))
         return [y0, y1, y2, y3]
 
@@ -102,22 +131,40 @@ class _DecoderConvUp(nn.Module):
         self.convtsp4 = nn.Sequential(*stage(192, 64, 5), *stage(64, 32, spec["k5"]), *tail, _Marker("sigmoid"))
 
     # -- engine forward: returns the channel-padded fp32 head Act [B,1,H,W,Np] ----
-    def _conv_relu_up(self, ctx, conv, x, skip=None):
+    def _conv_relu_up(self, ctx, conv, x, skip=None, cat=None):
         z = E.conv_forward(ctx, conv.plan(), x, act=L.ACT_RELU)
         zv = z.v
         if skip is None:
             return E.upsample2x_forward(ctx, z)
         sv = skip.v
         assert (sv.H, sv.W, sv.C) == (2 * zv.H, 2 * zv.W, zv.C), "skip connection shape mismatch"
-        cat = E.Act(E.View.alloc(zv.B, zv.T + sv.T, sv.H, sv.W, zv.C, ctx.dt, ctx.device), needs_grad=True)
+        if cat is None or (cat.v.B, cat.v.T, cat.v.H, cat.v.W, cat.v.C, cat.v.dt) != (zv.B, zv.T + sv.T, sv.H, sv.W, zv.C, ctx.dt):
+            cat = E.Act(E.View.alloc(zv.B, zv.T + sv.T, sv.H, sv.W, zv.C, ctx.dt, ctx.device), needs_grad=True)
         E.upsample2x_forward(ctx, z, cat.sub_t(0, zv.T))
+        # (no launch where the pool behind the skip has already written this slice: skip_concats)
         E.materialize(ctx, skip, cat.sub_t(zv.T, zv.T + sv.T), share_grad=True)
         return cat
 
-    def _fwd(self, ctx, y0, y1, y2, y3):
-        z = self._conv_relu_up(ctx, self.convtsp1[0], y0, y1)
-        z = self._conv_relu_up(ctx, self.convtsp2[0], z, y2)
-        z = self._conv_relu_up(ctx, self.convtsp3[0], z, y3)
+    def skip_concats(self, ctx, B, d0, skips):
+        """The three T-concat buffers [upsampled conv output | skip] of _fwd, allocated ahead of the encoder, and the skips'
+        slices of them: ([cat1, cat2, cat3], (slice for y1, for y2, for y3)).  d0: (T, H, W) of the decoder's first input;
+        skips: (T, H, W, C) of y1, y2, y3.  The extents follow from the convs' own out_dims; None when they do not fit."""
+        cats, keep, d = [], [], tuple(d0)
+        for conv, (sT, sH, sW, sC) in zip((self.convtsp1[0], self.convtsp2[0], self.convtsp3[0]), skips):
+            zT, zH, zW = conv.plan().out_dims(*d)
+            if zT < 1 or (sH, sW, sC) != (2 * zH, 2 * zW, conv.out_channels):
+                return None
+            cat = E.Act(E.View.alloc(B, zT + sT, sH, sW, sC, ctx.dt, ctx.device), needs_grad=True)
+            cats.append(cat)
+            keep.append(E.Act(cat.v.tslice(zT, zT + sT)))
+            d = (zT + sT, sH, sW)
+        return cats, tuple(keep)
+
+    def _fwd(self, ctx, y0, y1, y2, y3, cats=None):
+        c1, c2, c3 = cats if cats is not None else (None, None, None)
+        z = self._conv_relu_up(ctx, self.convtsp1[0], y0, y1, c1)
+        z = self._conv_relu_up(ctx, self.convtsp2[0], z, y2, c2)
+        z = self._conv_relu_up(ctx, self.convtsp3[0], z, y3, c3)
         z = self._conv_relu_up(ctx, self.convtsp4[0], z)
         z = self._conv_relu_up(ctx, self.convtsp4[3], z)
         convs = [m for m in list(self.convtsp4)[6:] if isinstance(m, ConvParams)]
@@ -219,9 +266,23 @@ class VideoSaliencyModel(nn.Module):
         self.num_hier = num_hier
         self.decoder = {8: DecoderConvUp8, 16: DecoderConvUp16, 32: DecoderConvUp, 48: DecoderConvUp48, 64: DecoderConvUp64}[num_clips]()
 
+    def _skip_concats(self, ctx, x, d0=None):
+        """(concat buffers, skip slices) for this clip where the encoder's pools write the decoder skips (engine.POOL_KEEPS_SKIP),
+        else (None, None).  d0: (T, H, W) of the decoder's first input where that is not y0 (the audio-visual models)"""
+        if not E.pool_keeps_skip(ctx):
+            return None, None
+        xv = x.v
+        H, W = x.fold if x.fold is not None else (xv.H, xv.W)
+        f = self.backbone.feature_dims(xv.T, H, W)
+        if min(min(d) for d in f) < 1:
+            return None, None
+        got = self.decoder.skip_concats(ctx, xv.B, f[0][:3] if d0 is None else d0, f[1:])
+        return got if got is not None else (None, None)
+
     def _fwd(self, ctx, x):
-        y0, y1, y2, y3 = self.backbone._fwd(ctx, x)
-        return self.decoder._fwd(ctx, y0, y1, y2, y3)
+        cats, keep = self._skip_concats(ctx, x)
+        y0, y1, y2, y3 = self.backbone._fwd(ctx, x, keep)
+        return self.decoder._fwd(ctx, y0, y1, y2, y3, cats)
 
     def forward(self, x):
         body = _MapBody(self, self._fwd, video=True)
@@ -345,7 +406,8 @@ class VideoAudioSaliencyModel(nn.Module):
     def _fwd(self, ctx, x, audio):
         from .fusion import bilinear_forward
         a = self.audionet._fwd(ctx, audio)                               # [B, 3, 1, 1, 1024]
-        y0, y1, y2, y3 = self.visual_model.backbone._fwd(ctx, x)
+        cats, keep = self.visual_model._skip_concats(ctx, x, (4, 7, 12))
+        y0, y1, y2, y3 = self.visual_model.backbone._fwd(ctx, x, keep)
         y0 = E.maxpool_forward(ctx, y0, (4, 1, 1), (2, 1, 2), (0, 0, 0))  # [B, 1, 7, 6, 1024]
         fused = bilinear_forward(ctx, self.bilinear, y0, a, (4, 7, 12))
         if self.use_transformer:
@@ -353,7 +415,7 @@ class VideoAudioSaliencyModel(nn.Module):
             tok = E.conv_forward(ctx, self.conv_in_1x1.plan(), fused)            # [B, 4, 7, 12, 32], bias, no BN, no ReLU
             tok = transformer_forward(ctx, self.transformer, tok)
             fused = E.conv_forward(ctx, self.conv_out_1x1.plan(), tok)
-        return self.visual_model.decoder._fwd(ctx, fused, y1, y2, y3)
+        return self.visual_model.decoder._fwd(ctx, fused, y1, y2, y3, cats)
 
     def forward(self, x, audio):
         body = _MapBody(self, self._fwd, video=True, audio=True)
@@ -420,14 +482,15 @@ class VideoAudioSaliencyFusionModel(nn.Module):
             raise ValueError("the fusion model runs on 32 x 224 x 384 clips (its 336 position tokens are y0's 4 x 7 x 12 positions, "
                              "model.py:143,180), got %d x %d x %d" % (xv.T, H, W))
         a = self.audionet._fwd(ctx, audio)                                # [B, 3, 1, 1, 1024]
-        y0, y1, y2, y3 = self.visual_model.backbone._fwd(ctx, x)          # y0 [B, 4, 7, 12, 1024]
+        cats, keep = self.visual_model._skip_concats(ctx, x, (4, 7, 12))
+        y0, y1, y2, y3 = self.visual_model.backbone._fwd(ctx, x, keep)    # y0 [B, 4, 7, 12, 1024]
         assert (a.v.T, a.v.H, a.v.W) == (self.N_AUDIO_TOKENS, 1, 1), "SoundNet gives %d time steps for this waveform, the model has 3 audio tokens" % a.v.T
         tokens, (vid, aud) = fusion.token_buffer(ctx, xv.B, [(4, 7, 12), (self.N_AUDIO_TOKENS, 1, 1)], self.conv_in_1x1.out_channels)
         E.conv_forward(ctx, self.conv_in_1x1.plan(), y0, dst=vid)
         E.conv_forward(ctx, self.audio_conv_1x1.plan(), a, dst=aud)
         enc = fusion.token_encoder_forward(ctx, self.transformer, tokens)
         fused = fusion.token_split_forward(ctx, enc, self.N_AUDIO_TOKENS, (4, 7, 12))
-        return self.visual_model.decoder._fwd(ctx, fused, y1, y2, y3)
+        return self.visual_model.decoder._fwd(ctx, fused, y1, y2, y3, cats)
 
     def forward(self, x, audio):
         body = _MapBody(self, self._fwd, video=True, audio=True)
