@@ -29,6 +29,22 @@ CS = (8, 24, 64, 192, 520)
 PLANES = ("real", "ties", "fan", "corner")
 
 
+class FusedPoolStubs:
+    """mixed into the CPU model of the ABI (tests/abi_emulator.py, which itself stays without them): the predicate and the two
+    fused entry points, built from the model's own pool backward and BatchNorm backward (the reduce stub stores dz as the pool
+    backward would, the apply stub continues from it).  For tests of what the ENGINE calls."""
+
+    def vinet_bn_bwd_pool_ok(self, pd, z, dp, dx, dtype):
+        return 1
+
+    def vinet_bn_bwd_reduce_pool(self, pd, dp, argmax, gacc, accumulate, z, dtype, fwd, mean, invstd, partials, stream):
+        rc = self.vinet_maxpool3d_bwd(pd, dp, argmax, gacc, accumulate, stream)
+        return rc or self.vinet_bn_bwd_reduce(gacc, z, dtype, fwd, mean, invstd, partials, stream)
+
+    def vinet_bn_bwd_apply_pool(self, pd, dp, argmax, gacc, accumulate, z, dtype, fwd, mean, invstd, c1, c2, dx, stream):
+        return self.vinet_bn_bwd_apply(gacc, z, dtype, fwd, mean, invstd, c1, c2, dx, stream)
+
+
 def pool_desc(dt=BF16, geo=K133):
     k, s, p = geo
     return L.CPoolDesc(dt, *k, *s, *p)

@@ -41,19 +41,8 @@ class _Net(_Block):
         return [out] if side is None else [out, side]
 
 
-class _Fused(AbiEmulator):
-    """a library object WITH the predicate and the two entry points, built from the model's own pool backward and BatchNorm backward
-    (the reduce stub stores dz as the pool backward would, the apply stub continues from it): what the engine calls is the point"""
-
-    def vinet_bn_bwd_pool_ok(self, pd, z, dp, dx, dtype):
-        return 1
-
-    def vinet_bn_bwd_reduce_pool(self, pd, dp, argmax, gacc, accumulate, z, dtype, fwd, mean, invstd, partials, stream):
-        rc = self.vinet_maxpool3d_bwd(pd, dp, argmax, gacc, accumulate, stream)
-        return rc or self.vinet_bn_bwd_reduce(gacc, z, dtype, fwd, mean, invstd, partials, stream)
-
-    def vinet_bn_bwd_apply_pool(self, pd, dp, argmax, gacc, accumulate, z, dtype, fwd, mean, invstd, c1, c2, dx, stream):
-        return self.vinet_bn_bwd_apply(gacc, z, dtype, fwd, mean, invstd, c1, c2, dx, stream)
+class _Fused(PC.FusedPoolStubs, AbiEmulator):
+    """a library object WITH the predicate and the two entry points (stubs: tests/bn_pool_cases.py): what the engine calls is the point"""
 
 
 def _step(lib, late, option, geo=K133, force_defer=False, monkeypatch=None):

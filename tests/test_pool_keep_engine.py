@@ -5,7 +5,7 @@ vinet_copy_affine launches disappear and nothing else changes: the same maps and
 the 1x3x3/s2 pool backwards are still formed inside the BatchNorm backward (engine.POOL_BWD_IN_BN).
 
 The CPU variant runs on the CPU model of the ABI (tests/abi_emulator.py) extended by this file's stubs of the keeping pool (the
-model's own pool + copy) and of the fused BatchNorm-pool entry points (as tests/test_bn_pool_host.py builds them): what the engine
+model's own pool + copy) and by the stubs of the fused BatchNorm-pool entry points (tests/bn_pool_cases.py): what the engine
 launches is the point there.  The GPU variant runs the library."""
 import collections
 
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from tests.abi_emulator import AbiEmulator, _deref
+from tests.bn_pool_cases import FusedPoolStubs
 from vinet_amd import _lib as L
 from vinet_amd import engine as E
 from vinet_amd import loss, model, synth
@@ -20,7 +21,7 @@ from vinet_amd import loss, model, synth
 SKIP_POOLS = 3
 
 
-class _Keeping(AbiEmulator):
+class _Keeping(FusedPoolStubs, AbiEmulator):
     def vinet_maxpool3d_keep_ok(self, pd, x, pre, y, argmax, keep):
         d, x, y, keep = _deref(pd), _deref(x), _deref(y), _deref(keep)
         k, s, p = (d.kT, d.kH, d.kW), (d.sT, d.sH, d.sW), (d.pT, d.pH, d.pW)
@@ -33,17 +34,6 @@ class _Keeping(AbiEmulator):
             return -1
         rc = self.vinet_maxpool3d(pd, x, pre, y, argmax, stream)
         return rc or self.vinet_copy_affine(x, _deref(pd).dtype, pre, keep, _deref(pd).dtype, 0, stream)
-
-    # (the fused BatchNorm-pool entry points, as in tests/test_bn_pool_host.py)
-    def vinet_bn_bwd_pool_ok(self, pd, z, dp, dx, dtype):
-        return 1
-
-    def vinet_bn_bwd_reduce_pool(self, pd, dp, argmax, gacc, accumulate, z, dtype, fwd, mean, invstd, partials, stream):
-        rc = self.vinet_maxpool3d_bwd(pd, dp, argmax, gacc, accumulate, stream)
-        return rc or self.vinet_bn_bwd_reduce(gacc, z, dtype, fwd, mean, invstd, partials, stream)
-
-    def vinet_bn_bwd_apply_pool(self, pd, dp, argmax, gacc, accumulate, z, dtype, fwd, mean, invstd, c1, c2, dx, stream):
-        return self.vinet_bn_bwd_apply(gacc, z, dtype, fwd, mean, invstd, c1, c2, dx, stream)
 
 
 def _step(dev, option):

@@ -49,7 +49,7 @@ for r in range(rounds):
     got = S.run(0, False)
     torch.cuda.synchronize()
     a, plan, bn = held["act"], held["plan"], held["bn"]
-    dy = a._grad.buf.float().view(-1, 1024)
+    dy = a.grad_view().buf.float().view(-1, 1024)
     sdy = dy.double().sum(0)
     gb = plan.bias.grad.double()
     d = (gb - sdy).abs()

@@ -18,6 +18,7 @@ Concepts
   Tape  list of backward closures recorded during a training forward; run in
         reverse by the single autograd node that wraps a root module call.
 """
+import collections
 import ctypes as C
 import itertools
 import math
@@ -307,20 +308,21 @@ class Act:
         # batch statistics of the training-mode BatchNorm(s) behind the pending affine (per channel, fp32; slices follow the
         # channel slices like scale / shift): what a consumer's data gradient needs to fold the BatchNorm-backward reduce pass in
         self.mean, self.invstd = mean, invstd
-        self._grad, self.grad_ready, self.needs_grad = None, False, needs_grad
+        self.needs_grad = needs_grad
         self.parent, self.pc0, self.pt0 = None, 0, 0
         self.fold = None
         self.indep = False       # channel region with its own "gradient written" flag (see region())
         self.ready_of = None     # span over several regions: ready when all of them are
-        self.grad_marks = 0      # writers of this gradient so far (mark_grad_ready calls on the root)
         self.alias_of = None     # the pending activation this plain one materialises with shared gradient storage (materialize)
-        self.n_readers = 0       # consumers recorded in this forward that will write this gradient (counted on the root)
         self.act_out = 0         # activation the producing conv applied in its epilogue (no BatchNorm): conv_forward
-        self.grad_masked = -1    # grad_marks at which the gradient already carries that activation's backward (upsample2x backward)
         self.prows = None        # (first row, T, H, W): a row range of the parent's positions under dims of its own (sub_rows)
         self.bn1 = False         # relu(bn(z)) of ONE recorded training-mode BatchNorm (conv_forward; not a joint conv's)
-        self.pool_rec = None     # on the owner of gradient storage: a max-pool backward into it that has not run (_PoolRec)
         self.kept_in = None      # the View that already holds this activation's materialised values (maxpool_forward, keep=)
+        # the gradient ledger's fields (the section below Act).  On the storage() owner: gradient storage, and a max-pool backward
+        # into it that has not run (_PoolRec).  On root(): written at all (or allocated zero-filled), writers so far, consumers
+        # recorded in this forward that will write, the stamp at which the gradient carried the backward of act_out (mask_grad)
+        self._grad, self.pool_rec = None, None
+        self.grad_ready, self.grad_marks, self.n_readers, self.grad_masked = False, 0, 0, -1
 
     @property
     def plain(self):
@@ -360,21 +362,27 @@ class Act:
         return a
 
     def root(self):
-        """owner of the gradient-ready flag"""
+        """owner of the gradient-ready flag and of the writer counts (the ledger below)"""
         a = self
         while a.parent is not None and not a.indep:
             a = a.parent
         return a
 
+    def storage(self):
+        """(owner of the gradient storage, absolute channel offset inside it); the offset is None when a T slice or a row range
+        lies on the way (decoder concat members, token rows: no BatchNorm there)"""
+        a, off = self, 0
+        while a.parent is not None:
+            off = None if off is None or a.pc0 is None else off + a.pc0
+            a = a.parent
+        return a, off
+
     # ---- gradients ------------------------------------------------------
     def grad_view(self, dt=None, zero=False):
         """gradient storage (allocated on first use; slices resolve into the parent's)."""
         if self.parent is not None:
-            if self.indep and zero:
-                top = self.parent
-                while top.parent is not None:
-                    top = top.parent
-                assert top._grad is None, "zero-filled gradient requested for a region of live shared storage"
+            assert not (self.indep and zero) or self.storage()[0]._grad is None, \
+                "zero-filled gradient requested for a region of live shared storage"
             g = self.parent.grad_view(dt, zero)
             if self.prows is not None:
                 r0, t, h, w = self.prows
@@ -384,7 +392,8 @@ class Act:
             return g.tslice(self.pt0, self.pt0 + self.v.T)
         if self.pool_rec is not None:
             # somebody other than the BatchNorm backward the deferred pool backward waits for wants this gradient: it runs now
-            self.pool_rec.flush(self)
+            rec, self.pool_rec = self.pool_rec, None         # (first: the launch asks for the gradient view itself)
+            rec.launch(rec.acc)
         if self._grad is None:
             v = self.v
             self._grad = View.alloc(v.B, v.T, v.H, v.W, v.C, v.dt if dt is None else dt, v.device, zero=zero)
@@ -403,32 +412,75 @@ class Act:
         r.grad_marks += 1
 
 
-class _PoolRec:
-    """a 1x3x3/s2 max-pool backward that did NOT run (maxpool_forward, POOL_BWD_IN_BN): the pool was the last writer of the gradient
-    of x = relu(bn(z)), so the BatchNorm backward of x's producer forms that gradient in registers from (dp, argmax, what the
-    buffer holds) -- _bn_backward.  The record sits on the Act that owns the gradient STORAGE: every access to that storage, through
-    any slice or alias, passes its grad_view(), which runs the ordinary pool backward first unless _take_pool_rec got there before."""
-    __slots__ = ("x", "pd", "dp", "am", "acc", "launch")
+# ----------------------------------------------------------------------------
+# the gradient ledger: who has written a gradient, who still will, and is what somebody remembered about it still true?
+# Act's own methods above and this section are the only code that reads or writes _grad, grad_ready, grad_marks, n_readers,
+# grad_masked and pool_rec.  Counts, stamps and the ready flag live on Act.root(); storage and a deferred writer on Act.storage()[0].
+# ----------------------------------------------------------------------------
 
-    def __init__(self, x, pd, dp, am, acc, launch):
-        self.x, self.pd, self.dp, self.am, self.acc, self.launch = x, pd, dp, am, acc, launch
-
-    def flush(self, owner):
-        owner.pool_rec = None        # (first: the launch asks for the gradient view itself)
-        self.launch(self.acc)
+def note_reader(ctx, x):
+    """forward: one more consumer of `x` whose backward will write x's gradient"""
+    if ctx.recording and x.needs_grad:
+        x.root().n_readers += 1
 
 
-def _grad_owner(a):
-    """the Act that owns the gradient storage of `a`"""
-    while a.parent is not None:
-        a = a.parent
-    return a
+def writers_left(x):
+    """consumers recorded in forward that have not yet written x's gradient: 1 inside the backward of the LAST writer"""
+    r = x.root()
+    return r.n_readers - r.grad_marks
+
+
+def grad_stamp(x):
+    """what somebody remembers about x's gradient holds until its next writer: unwritten_since(x, the stamp of that moment)"""
+    return x.root().grad_marks
+
+
+def unwritten_since(x, stamp):
+    return x.root().grad_marks == stamp
+
+
+def mask_grad(x):
+    """x's gradient, as just written, already carries the backward of x's own activation (upsample2x_forward)"""
+    x.grad_masked = grad_stamp(x)
+
+
+def grad_is_masked(x):
+    return unwritten_since(x, x.grad_masked)
+
+
+def adopt_grad(a, v):
+    """`v` holds a's gradient, written (a standalone conv backward, ops.py)"""
+    a._grad, a.grad_ready = v, True
+
+
+def _can_rehome(a):
+    return a.parent is None and a._grad is None         # (it owns its gradient storage, and has none yet)
+
+
+def _rehome(a, onto):
+    """a's gradient lives in onto's from now on (an identity "slice": grad_view and readiness resolve into onto's), and the
+    consumers of `a` noted so far will write there"""
+    a.parent, a.pc0, a.pt0 = onto, 0, None
+    onto.root().n_readers += a.n_readers
+    a.n_readers = 0
+
+
+# a 1x3x3/s2 max-pool backward that did NOT run (maxpool_forward, POOL_BWD_IN_BN): the pool was the last writer of the gradient of
+# x = relu(bn(z)), so the BatchNorm backward of x's producer forms that gradient in registers from (dp, argmax, what the buffer
+# holds) -- _bn_backward_sums, _bn_backward_apply.  The record sits on the Act that owns the gradient STORAGE: every access to it,
+# through any slice or alias, passes its grad_view(), which runs the ordinary pool backward first unless _take_pool_rec got there before.
+_PoolRec = collections.namedtuple("_PoolRec", "x pd dp am acc launch")
+
+
+def _defer_pool(rec):
+    rec.x.storage()[0].pool_rec = rec
+    rec.x.mark_grad_ready()
 
 
 def _take_pool_rec(res, bn, train_bn, x):
     """the deferred pool backward into the gradient of `res`, for the BatchNorm backward of res's producer to fold in; None (and the
     record, if any, stays: res.grad_view() will run it) unless it is exactly this layer's"""
-    owner = _grad_owner(res)
+    owner = res.storage()[0]
     rec = owner.pool_rec
     if rec is None or rec.x is not res or bn is None or isinstance(bn, JointBN) or not train_bn or not x.needs_grad:
         return None
@@ -436,48 +488,27 @@ def _take_pool_rec(res, bn, train_bn, x):
     return rec
 
 
-def _abs_chan(a):
-    """(storage owner, absolute channel offset) of an activation inside the buffer that owns its gradient storage; None when a
-    T slice lies on the way (decoder concat members: no BatchNorm there)"""
-    off = 0
-    while a.parent is not None:
-        if a.pc0 is None:
-            return None
-        off += a.pc0
-        a = a.parent
-    return a, off
-
-
-def _note_reader(ctx, x):
-    """forward: one more consumer of `x` whose backward will write x's gradient"""
-    if ctx.recording and x.needs_grad:
-        x.root().n_readers += 1
-
-
 def _register_bnb(ctx, x, ws, rows):
     """a data gradient just wrote x's gradient (already marked) together with the BatchNorm-backward partial sums `ws`
-    ([rows][2][x.C]) of the layer(s) behind x's pending affine: remember them with the writer count of that moment -- they are
+    ([rows][2][x.C]) of the layer(s) behind x's pending affine: remember them with the stamp of that moment -- they are
     valid as long as no later writer touches the gradient (_find_bnb checks)"""
-    loc = _abs_chan(x)
-    if loc is None:
+    owner, off = x.storage()
+    if off is None:
         return
-    owner, off = loc
-    r = x.root()
     # (kept on the pass, not on the activation: an Act that referenced its own root would be a reference cycle, and a step's
     #  activations must die by reference count when the tape is dropped -- 190 GB of them at the headline batch)
-    ctx._bnb.setdefault(id(owner), []).append((off, off + x.v.C, ws, rows, r, r.grad_marks))
+    ctx._bnb.setdefault(id(owner), []).append((off, off + x.v.C, ws, rows, x.root(), grad_stamp(x)))
 
 
 def _find_bnb(ctx, res, c0, width):
     """partial sums covering channels [c0, c0 + width) of `res` left by the LAST writer of that gradient: (ws, rows, column offset,
     row width) or None"""
-    loc = _abs_chan(res)
-    if loc is None or id(loc[0]) not in ctx._bnb:
+    owner, off = res.storage()
+    if off is None or id(owner) not in ctx._bnb:
         return None
-    owner, off = loc
     a0, a1 = off + c0, off + c0 + width
-    for r0, r1, ws, rows, root, marks in reversed(ctx._bnb[id(owner)]):
-        if r0 <= a0 and a1 <= r1 and root.grad_marks == marks:
+    for r0, r1, ws, rows, root, stamp in reversed(ctx._bnb[id(owner)]):
+        if r0 <= a0 and a1 <= r1 and unwritten_since(root, stamp):
             return ws, rows, a0 - r0, r1 - r0
     return None
 
@@ -496,6 +527,11 @@ class Ctx:
         self.stream = _stream_for(device)
         self._bnb = {}           # id(storage owner) -> [(c0, c1, partials, rows, root, marks)]: BN-backward partial sums that data gradients left
         self._side_rr = -1       # weight-gradient stream the last job went to (jobs are dealt round robin)
+        # optional entry points of this library object, asked once per pass (maxpool_forward, _pool_bwd_defers)
+        lib = self.lib
+        self.lib_keeps = getattr(lib, "vinet_maxpool3d_keep_ok", None) is not None and hasattr(lib, "vinet_maxpool3d_keep")
+        self.lib_pools_in_bn = (getattr(lib, "vinet_bn_bwd_pool_ok", None) is not None and hasattr(lib, "vinet_bn_bwd_reduce_pool")
+                                and hasattr(lib, "vinet_bn_bwd_apply_pool"))
         self._begin_backward()
 
     def _begin_backward(self, capturing=False):
@@ -753,14 +789,14 @@ def materialize(ctx, a, dst=None, out_dt=None, share_grad=False):
         ctx.call("vinet_copy_affine", C.byref(v.ct()), v.dt, a.affine(), C.byref(out.ct()), out.dt, 0, ctx.stream)
     dst.needs_grad = a.needs_grad
     if alias:
-        dst.parent, dst.pc0, dst.pt0 = a, 0, None        # identity "slice": grad_view / readiness resolve into a's
+        _rehome(dst, a)
         dst.alias_of = a
         return dst
-    _note_reader(ctx, a)
-    if (share_grad and SHARE_SKIP_GRAD and ctx.recording and a.needs_grad and a.parent is None and a._grad is None
+    if (share_grad and SHARE_SKIP_GRAD and ctx.recording and a.needs_grad and _can_rehome(a)
             and dst.parent is not None and out.dt == v.dt):
-        a.parent, a.pc0, a.pt0 = dst, 0, None            # a's gradient lives in dst's slice of the concat gradient
+        _rehome(a, dst)         # a's gradient lives in dst's slice of the concat gradient (this pass never writes it: no reader)
         return dst
+    note_reader(ctx, a)
     if ctx.recording and a.needs_grad:
         def bwd():
             dg = dst.grad_view()
@@ -1280,7 +1316,7 @@ def conv_forward(ctx, plan, x, bn=None, act=L.ACT_NONE, dst=None, out_dt=None, n
     `dst`         : optional destination Act (channel / T slice of a concat buffer).
     `n_pad`       : store into a channel-padded output (N not a multiple of the vector width).
     """
-    _note_reader(ctx, x)
+    note_reader(ctx, x)
     want_plain = (MATERIALIZE_NT and x.scale is not None and ctx.dt != L.F32 and x.fold is None and not plan.stem and
                   plan.N * plan.ntaps >= MATERIALIZE_NT and x.v.dt == ctx.dt)
     xv = x.v
@@ -1454,7 +1490,8 @@ def _conv_backward(ctx, plan, x, res, bn, act, train_bn, keep, M):
     assert res.is_grad_ready(), "conv backward reached before any consumer produced a gradient"
     fused_bnb = dy_planes = None
     if bn is not None:
-        dy, fused_bnb, dy_planes = _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz, pool)
+        sums = _bn_backward_sums(ctx, res, bn, train_bn, keep, M, dz, pool)
+        dy, fused_bnb, dy_planes = _bn_backward_apply(ctx, plan, x, res, keep, dz, pool, *sums)
     else:
         dy = _act_backward(ctx, res, act, dz)
     if plan.bias is not None and plan.bias.requires_grad:
@@ -1467,37 +1504,20 @@ def _conv_backward(ctx, plan, x, res, bn, act, train_bn, keep, M):
         _data_grad(ctx, plan, x, res.v, dy, M)
 
 
-def _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz, pool=None):
-    """stage 1 behind a BatchNorm: dz (w.r.t. the BN + ReLU output) -> dy (w.r.t. the raw conv output), in place.  Returns
-    (dy, fused, planes): `fused` = (z, forward affine, mean, invstd, c1, c2) when the weight-gradient kernel forms dy on the fly
-    and no apply pass ran (else None); `planes` = the fp32s (hi, lo) bf16 planes of dy the apply pass wrote (else None)"""
+def _bn_backward_sums(ctx, res, bn, train_bn, keep, M, dz, pool):
+    """stage 1 behind a BatchNorm, first half: c1, c2 per BatchNorm behind this conv (one, or the members of a joint entry conv).
+    Its two backward sums either came with the gradient -- the data gradient that wrote dz LAST left their partial rows
+    (VinetConvDesc::bnb_*; _find_bnb checks that no writer came after it) -- or need a reduce pass over (dz, z).  pool: dz does not
+    exist -- the last writer of this gradient, a 1x3x3/s2 max-pool backward, was deferred (_PoolRec); both halves form it from
+    (dp, argmax, the buffer's contents when accumulating)"""
     out, Ny = res.v, res.v.C
-    fwd = res.affine()
     mean, invstd = keep["mean"], keep["invstd"]
     nb = float(dz.nvox * dz.C * ESIZE[dz.dt])
-    if pool is not None:
-        # dz does not exist: the last writer of this gradient, a 1x3x3/s2 max-pool backward, was deferred (_PoolRec).  Both passes
-        # form it from (dp, argmax, the buffer's contents when accumulating); the apply pass writes dy where dz would have been.
-        nq = float(pool.dp.nvox * dz.C)                      # dp (2 bytes) and the argmax codes (1) per pooled element
-        rows = ctx.lib.vinet_stats_rows(C.byref(out.ct()))
-        ws = ctx.f32(rows * 2 * Ny)
-        c1, c2 = ctx.f32(Ny), ctx.f32(Ny)
-        ctx.call("vinet_bn_bwd_reduce_pool", C.byref(pool.pd), C.byref(pool.dp.ct()), pool.am.data_ptr(), C.byref(dz.ct()), pool.acc,
-                 C.byref(out.ct()), dz.dt, fwd, mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ctx.stream,
-                 tag=_bn_tag("reduce", Ny, dz, " pool"), work=dict(flops=0.0, bytes=(1 + pool.acc) * nb + 3 * nq))
-        bn.bwd_finalize(ctx, ws, rows, Ny, M, res.scale, train_bn, invstd, c1, c2, off=0, ld=Ny, ws_off=0)
-        ctx.call("vinet_bn_bwd_apply_pool", C.byref(pool.pd), C.byref(pool.dp.ct()), pool.am.data_ptr(), C.byref(dz.ct()), pool.acc,
-                 C.byref(out.ct()), dz.dt, fwd, mean.data_ptr(), invstd.data_ptr(), c1.data_ptr(), c2.data_ptr(), C.byref(dz.ct()),
-                 ctx.stream, tag=_bn_tag("apply", Ny, dz, " pool"), work=dict(flops=0.0, bytes=(2 + pool.acc) * nb + 3 * nq))
-        return dz, None, None
-    # per BatchNorm behind this conv (one, or the members of a joint entry conv): its two backward sums either came with the
-    # gradient -- the data gradient that wrote dz LAST left their partial rows (VinetConvDesc::bnb_*; _find_bnb checks that
-    # no writer came after it) -- or need a reduce pass over (dz, z)
     members = list(zip(bn.members, bn.offs, bn.widths)) if isinstance(bn, JointBN) else [(bn, 0, Ny)]
     c1, c2 = ctx.f32(Ny), ctx.f32(Ny)
     left = []
     for m_, o_, w_ in members:
-        part = _find_bnb(ctx, res, o_, w_) if DGRAD_BN_STATS else None
+        part = _find_bnb(ctx, res, o_, w_) if DGRAD_BN_STATS and pool is None else None
         if part is None:
             left.append((m_, o_, w_))
         else:
@@ -1506,14 +1526,36 @@ def _bn_backward(ctx, plan, x, res, bn, train_bn, keep, M, dz, pool=None):
     regions = [(0, Ny, left)] if len(left) == len(members) else [(o_, w_, [(m_, o_, w_)]) for m_, o_, w_ in left]
     for r0, rw, mem in regions:
         dzs, outs = (dz, out) if rw == Ny else (dz.chan(r0, r0 + rw), out.chan(r0, r0 + rw))
-        rows = ctx.lib.vinet_stats_rows(C.byref(dzs.ct()))
+        rows = ctx.lib.vinet_stats_rows(C.byref((dzs if pool is None else outs).ct()))
         ws = ctx.f32(rows * 2 * rw)
-        fsl = L.CAffine(res.scale.data_ptr() + 4 * r0, res.shift.data_ptr() + 4 * r0, 1 if res.relu else 0)
-        ctx.call("vinet_bn_bwd_reduce", C.byref(dzs.ct()), C.byref(outs.ct()), dz.dt, fsl, mean.data_ptr() + 4 * r0,
-                 invstd.data_ptr() + 4 * r0, ws.data_ptr(), ctx.stream, tag=_bn_tag("reduce", rw, dz),
-                 work=dict(flops=0.0, bytes=2 * nb * rw / Ny))
+        if pool is not None:        # (one BatchNorm, the whole tensor: _take_pool_rec)
+            nq = float(pool.dp.nvox * dz.C)                  # dp (2 bytes) and the argmax codes (1) per pooled element
+            ctx.call("vinet_bn_bwd_reduce_pool", C.byref(pool.pd), C.byref(pool.dp.ct()), pool.am.data_ptr(), C.byref(dz.ct()), pool.acc,
+                     C.byref(out.ct()), dz.dt, res.affine(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(), ctx.stream,
+                     tag=_bn_tag("reduce", Ny, dz, " pool"), work=dict(flops=0.0, bytes=(1 + pool.acc) * nb + 3 * nq))
+        else:
+            fsl = L.CAffine(res.scale.data_ptr() + 4 * r0, res.shift.data_ptr() + 4 * r0, 1 if res.relu else 0)
+            ctx.call("vinet_bn_bwd_reduce", C.byref(dzs.ct()), C.byref(outs.ct()), dz.dt, fsl, mean.data_ptr() + 4 * r0,
+                     invstd.data_ptr() + 4 * r0, ws.data_ptr(), ctx.stream, tag=_bn_tag("reduce", rw, dz),
+                     work=dict(flops=0.0, bytes=2 * nb * rw / Ny))
         for m_, o_, w_ in mem:
             m_.bwd_finalize(ctx, ws, rows, w_, M, res.scale, train_bn, invstd, c1, c2, off=o_, ld=rw, ws_off=o_ - r0)
+    return c1, c2
+
+
+def _bn_backward_apply(ctx, plan, x, res, keep, dz, pool, c1, c2):
+    """... second half: dz (w.r.t. the BN + ReLU output) -> dy (w.r.t. the raw conv output), in place, by one of four routes.
+    Returns (dy, fused, planes): `fused` = (z, forward affine, mean, invstd, c1, c2) when the weight-gradient kernel forms dy on
+    the fly and no apply pass ran (else None); `planes` = the fp32s (hi, lo) bf16 planes of dy the apply pass wrote (else None)"""
+    out, fwd = res.v, res.affine()
+    mean, invstd = keep["mean"], keep["invstd"]
+    nb = float(dz.nvox * dz.C * ESIZE[dz.dt])
+    if pool is not None:        # (the pooled form writes dy where dz would have been)
+        nq = float(pool.dp.nvox * dz.C)
+        ctx.call("vinet_bn_bwd_apply_pool", C.byref(pool.pd), C.byref(pool.dp.ct()), pool.am.data_ptr(), C.byref(dz.ct()), pool.acc,
+                 C.byref(out.ct()), dz.dt, fwd, mean.data_ptr(), invstd.data_ptr(), c1.data_ptr(), c2.data_ptr(), C.byref(dz.ct()),
+                 ctx.stream, tag=_bn_tag("apply", dz.C, dz, " pool"), work=dict(flops=0.0, bytes=(2 + pool.acc) * nb + 3 * nq))
+        return dz, None, None
     # A conv whose input needs no gradient (the RGB stem) has one consumer of dz, its weight gradient: kernels
     # that can form dz from (gradient behind the BN, raw conv output) on the fly spare the apply pass
     if BN_BWD_FUSE and not x.needs_grad and plan.wants_wgrad() and plan.bias is None and out.dt == dz.dt == ctx.dt:
@@ -1543,7 +1585,7 @@ def _bn_tag(what, width, dz, mark=""):
 
 def _act_backward(ctx, res, act, dz):
     """stage 1 without a BatchNorm: dz -> dy through the conv's own activation, in the arithmetic's storage type"""
-    if act == L.ACT_RELU and res.grad_masked == res.root().grad_marks and dz.dt == ctx.dt:
+    if act == L.ACT_RELU and grad_is_masked(res) and dz.dt == ctx.dt:
         return dz       # the only writer of dz (the upsample's backward) already gated it with this ReLU
     if act == L.ACT_NONE and dz.dt == ctx.dt:
         return dz
@@ -1574,7 +1616,7 @@ class _WgradJob:
 
     def __init__(self, ctx, plan, x, dy, M, bn_free, fused_bnb, dy_planes):
         self.ctx, self.plan, self.x, self.dy, self.M, self.bn_free = ctx, plan, x, dy, M, bn_free
-        self.fused_bnb, self.dy_planes = fused_bnb, dy_planes       # what stage 1 left: _bn_backward
+        self.fused_bnb, self.dy_planes = fused_bnb, dy_planes       # what stage 1 left: _bn_backward_apply
         # fp32s: hi / lo planes of both operands for the three bf16 launches -- any conv with whole 8-channel groups, and the
         # folded RGB stem (the row-streaming strip kernel, wgrad_hs.hip, over planes of the padded clip)
         self.want_planes = bool(SPLIT_WGRAD_BF16 and ctx.cdt == F32S and fused_bnb is None and dy.C % 8 == 0 and x.v.dt == F32 and dy.dt == F32 and
@@ -1717,7 +1759,7 @@ def _data_grad(ctx, plan, x, out, dy, M):
     bx = x.alias_of if x.alias_of is not None else x
     want_bnb = (DGRAD_BN_STATS >= 2 and len(phases) == 1 and full and bx.mean is not None and bx.scale is not None and bx.relu
                 and bx.fold is None and ctx.cdt == BF16 and dx.dt == BF16 and bx.v.dt == BF16 and xv.C == plan.Cin
-                and dx.same_dims(bx.v) and x.root().grad_marks + 1 == x.root().n_readers)
+                and dx.same_dims(bx.v) and writers_left(x) == 1)
     part = None
     for ph in phases:
         d = _conv_desc(ctx, L.CONV_GENERIC, dy, dx, ph["Q"], (1, 1, 1), plan.s, ph["r"], ph["ntaps"], ph["taps"], wt, plan.kp(True),
@@ -1737,8 +1779,7 @@ def _data_grad(ctx, plan, x, out, dy, M):
 
 def pool_keeps_skip(ctx):
     """do the pools behind the decoder skips write the skips' materialised values themselves (maxpool_forward, keep=)?"""
-    return bool(POOL_KEEPS_SKIP) and ctx.dt == BF16 and getattr(ctx.lib, "vinet_maxpool3d_keep_ok", None) is not None \
-        and hasattr(ctx.lib, "vinet_maxpool3d_keep")
+    return bool(POOL_KEEPS_SKIP) and ctx.dt == BF16 and ctx.lib_keeps
 
 
 def maxpool_forward(ctx, x, k, s, p, dst=None, keep=None):
@@ -1753,7 +1794,7 @@ def maxpool_forward(ctx, x, k, s, p, dst=None, keep=None):
     assert (out.T, out.H, out.W, out.C) == (od[0], od[1], od[2], xv.C) and dst.plain
     pd = L.CPoolDesc(xv.dt, k[0], k[1], k[2], s[0], s[1], s[2], p[0], p[1], p[2])
     rec = ctx.recording and x.needs_grad
-    _note_reader(ctx, x)
+    note_reader(ctx, x)
     am = torch.empty(out.nvox * out.C, dtype=torch.uint8, device=xv.device) if rec else None
     ptag = "maxpool k%dx%dx%d s%dx%dx%d C%d in%dx%dx%dx%d" % (k + s + (xv.C, xv.B, xv.T, xv.H, xv.W))
     es = ESIZE[xv.dt]
@@ -1780,14 +1821,13 @@ def maxpool_forward(ctx, x, k, s, p, dst=None, keep=None):
 
         def bwd():
             acc = 1 if x.is_grad_ready() else 0
-            if _pool_bwd_defers(ctx, x, pd, k, s, p):
+            if _pool_bwd_defers(ctx, x, pd):
                 dy, dx = dst.grad_view(), x.grad_view()
                 if dy.dt == dx.dt == BF16 and ctx.lib.vinet_bn_bwd_pool_ok(C.byref(pd), C.byref(xv.ct()), C.byref(dy.ct()),
                                                                           C.byref(dx.ct()), xv.dt):
-                    # the BatchNorm backward of x's producer forms this gradient itself (_bn_backward); anybody else who asks for
+                    # the BatchNorm backward of x's producer forms this gradient itself (_bn_backward_sums); anybody else who asks for
                     # it first gets the ordinary launch (Act.grad_view)
-                    _grad_owner(x).pool_rec = _PoolRec(x, pd, dy, am, acc, launch)
-                    x.mark_grad_ready()
+                    _defer_pool(_PoolRec(x, pd, dy, am, acc, launch))
                     return
             launch(acc)
             x.mark_grad_ready()
@@ -1795,22 +1835,18 @@ def maxpool_forward(ctx, x, k, s, p, dst=None, keep=None):
     return dst
 
 
-def _pool_bwd_defers(ctx, x, pd, k, s, p):
+def _pool_bwd_defers(ctx, x, pd):
     """may this pool backward be left to the BatchNorm backward behind x?  x = relu(bn(z)) of one recorded training-mode BatchNorm,
     bf16 arithmetic, the 1x3x3 / s(1,2,2) / p(0,1,1) pool, a library with the fused kernels -- and the pool is the LAST writer of
     x's gradient: every other consumer recorded in forward has written.  A gradient that lives in a decoder concat's (materialize,
-    share_grad) counts the concat's consumers and, the sharing one apart, x's own."""
+    share_grad) counts the concat's consumers and x's own."""
     if not (POOL_BWD_IN_BN and x.bn1 and x.relu and x.scale is not None and x.mean is not None and x.fold is None and x.prows is None
-            and x.alias_of is None and ctx.cdt == BF16 and x.v.dt == BF16 and (k, s, p) == ((1, 3, 3), (1, 2, 2), (0, 1, 1))
-            and getattr(ctx.lib, "vinet_bn_bwd_pool_ok", None) is not None and hasattr(ctx.lib, "vinet_bn_bwd_reduce_pool")
-            and hasattr(ctx.lib, "vinet_bn_bwd_apply_pool")):
+            and x.alias_of is None and ctx.cdt == BF16 and x.v.dt == BF16 and ctx.lib_pools_in_bn
+            and (pd.kT, pd.kH, pd.kW, pd.sT, pd.sH, pd.sW, pd.pT, pd.pH, pd.pW) == (1, 3, 3, 1, 2, 2, 0, 1, 1)):
         return False
-    r = x.root()
-    if r is x:
-        return x.parent is None and r.grad_marks + 1 == r.n_readers
-    if x.indep or x.pc0 != 0 or x.pt0 is not None or x.parent.v.C != x.v.C:
+    if x.parent is not None and (x.indep or x.pc0 != 0 or x.pt0 is not None or x.parent.v.C != x.v.C):
         return False            # (a concat member: other layers write into the same root)
-    return r.grad_marks + 1 == r.n_readers + x.n_readers - 1
+    return writers_left(x) == 1
 
 
 def upsample2x_forward(ctx, x, dst=None):
@@ -1821,7 +1857,7 @@ def upsample2x_forward(ctx, x, dst=None):
     out = dst.v
     assert dst.plain
     ctx.call("vinet_upsample2x", C.byref(xv.ct()), C.byref(out.ct()), xv.dt, ctx.stream)
-    _note_reader(ctx, x)
+    note_reader(ctx, x)
     dst.needs_grad = x.needs_grad
     if ctx.recording and x.needs_grad:
         def bwd():
@@ -1832,7 +1868,7 @@ def upsample2x_forward(ctx, x, dst=None):
                 # backward goes with it (no vinet_act_bwd pass in the conv's backward)
                 ctx.call("vinet_upsample2x_bwd_relu", C.byref(dy.ct()), C.byref(dx.ct()), C.byref(xv.ct()), dx.dt, ctx.stream)
                 x.mark_grad_ready()
-                x.grad_masked = x.root().grad_marks
+                mask_grad(x)
                 return
             ctx.call("vinet_upsample2x_bwd", C.byref(dy.ct()), C.byref(dx.ct()), dx.dt, 1 if x.is_grad_ready() else 0, ctx.stream)
             x.mark_grad_ready()
@@ -1943,7 +1979,7 @@ class BlockBody:
         outs = self.fwd(ectx, *acts)
         outs = list(outs) if isinstance(outs, (list, tuple)) else [outs]
         for o in outs:
-            _note_reader(ectx, o)        # (the seed of backward writes its gradient: import_grad_ncdhw)
+            note_reader(ectx, o)       # (the seed of backward writes its gradient: import_grad_ncdhw)
         tens = [export_ncdhw(ectx, o, self.out_channels(o)) for o in outs]
         return tens, (acts, outs, [t.shape[1] for t in inputs])
 

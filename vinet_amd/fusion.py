@@ -14,8 +14,8 @@ def bilinear_forward(ctx, bil, y0, audio, out_thw):
     Act [B,4,7,12,C] with out[b, o, c] = sum_ij x1[b,i,c] W[o,i,j] x2[b,j,c] + bias[o]."""
     x1 = E.materialize(ctx, y0) if not _dense_plain(y0) else y0
     x2 = E.materialize(ctx, audio) if not _dense_plain(audio) else audio
-    E._note_reader(ctx, x1)
-    E._note_reader(ctx, x2)
+    E.note_reader(ctx, x1)
+    E.note_reader(ctx, x2)
     v1, v2 = x1.v, x2.v
     B, Cc = v1.B, v1.C
     I, J = v1.T * v1.H * v1.W, v2.T * v2.H * v2.W
@@ -62,7 +62,7 @@ def transformer_forward(ctx, tf, x, masks=None):
     without gradients, like nn.Dropout) draws dropout masks from (tf.dropout_seed, the device step counter); `masks` (uint8, tf.mask_bytes(B)) receives them."""
     if not _dense_plain(x):
         x = E.materialize(ctx, x)
-    E._note_reader(ctx, x)
+    E.note_reader(ctx, x)
     xv = x.v
     layers = list(tf.transformer_encoder.layers)
     l0 = layers[0]
@@ -137,7 +137,7 @@ def token_encoder_forward(ctx, tf, tokens, out=None, masks=None):
     may be a channel sub-view of a wider tensor): PositionalEncoding + the encoder stack of `tf` (model._TransformerParams with
     pe [S,1,E]).  Dropout as transformer_forward; `masks` (uint8, tf.mask_bytes(B)) receives the keep masks."""
     assert tokens.plain, "the token encoder reads plain activations"
-    E._note_reader(ctx, tokens)
+    E.note_reader(ctx, tokens)
     xv = tokens.v
     layers = list(tf.transformer_encoder.layers)
     l0 = layers[0]
@@ -191,7 +191,7 @@ def token_split_forward(ctx, tokens, n_audio, out_thw):
     """encoder output [B, Sv + n_audio rows, E] -> the decoder's input [B, T, H, W, 2E] (T H W = Sv): the video rows in channels
     [0, E), the mean of the audio rows in channels [E, 2E) at every position (model.py:175-185)"""
     assert tokens.plain
-    E._note_reader(ctx, tokens)
+    E.note_reader(ctx, tokens)
     xv = tokens.v
     T, H, W = out_thw
     assert xv.T * xv.H * xv.W == T * H * W + n_audio

@@ -78,7 +78,7 @@ def _standalone_backward(x, dy, weight, stride, padding, want_dx, want_dw):
     plan = _plan(w, None, stride, padding)
     xa = E.Act(_view(x), needs_grad=want_dx)
     res = E.Act(_view(dy))
-    res._grad, res.grad_ready = res.v, True
+    E.adopt_grad(res, res.v)
     M = dy.shape[0] * dy.shape[1] * dy.shape[2] * dy.shape[3]
     E._conv_backward(ctx, plan, xa, res, None, L.ACT_NONE, False, {}, M)
     ctx.finish_backward()
