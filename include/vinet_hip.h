@@ -629,6 +629,26 @@ typedef struct VinetTokenEncoderDesc {
 int64_t vinet_token_encoder_workspace(const VinetTokenEncoderDesc* desc);
 int vinet_token_encoder_fwd(const VinetTokenEncoderDesc* desc, const VinetTensor* x, const VinetTensor* y, void* stream);
 int vinet_token_encoder_bwd(const VinetTokenEncoderDesc* desc, const VinetTensor* dy, const VinetTensor* dx, void* stream);
+/* Arithmetic of the encoder's LINEAR products (the six linears of a layer with their data and weight gradients; attention,
+ * softmax, LayerNorm, epilogues, workspace and saved activations stay fp32 in every mode), chosen per call whatever `dtype` is:
+ *   VINET_TK_MMA_F32     exact fp32 products on the fp32-input MFMA: what the three entry points above run.
+ *   VINET_TK_MMA_BF16X3  fp32 matrices, bf16 matrix arithmetic on the two-term split of both operands that VINET_F32S names
+ *                        (a = hi + lo, hi = bf16(a) to nearest even, lo = bf16(a - hi), 16 significant bits;
+ *                        hi*hi + hi*lo + lo*hi, fp32 accumulate) -- 3/16 of the fp32-MFMA cost, error ~2^-17 per operand.
+ *   VINET_TK_MMA_BF16    hi*hi alone, fp32 accumulate: 1/16 of the fp32-MFMA cost, error ~2^-9 per operand.
+ * The operands are rounded while they are staged; nothing rounded is stored.  The dropout keep masks of a step do not depend on
+ * the mode.  The workspace has one size for all modes.  Backward must be given the mode of its forward.  An unknown mode: -1. */
+enum { VINET_TK_MMA_F32 = 0, VINET_TK_MMA_BF16X3 = 1, VINET_TK_MMA_BF16 = 2 };
+int64_t vinet_token_encoder_workspace_mma(const VinetTokenEncoderDesc* desc, int32_t mma);
+int vinet_token_encoder_fwd_mma(const VinetTokenEncoderDesc* desc, int32_t mma, const VinetTensor* x, const VinetTensor* y, void* stream);
+int vinet_token_encoder_bwd_mma(const VinetTokenEncoderDesc* desc, int32_t mma, const VinetTensor* dy, const VinetTensor* dx, void* stream);
+/* one linear product of the encoder, any mode (mma = F32 runs tf_gemm): form 0 C[m][n] = sum_k A[m][k] B[n][k],
+ * form 1 sum_k A[m][k] B[k][n], form 2 sum_k A[k][m] B[k][n]; epi 0 plain, 1 + bias[n], 2 relu(. + bias), 3 + res[m][ldc], 4 C +=.
+ * fp32 matrices with row strides lda / ldb / ldc (elements); M % 4 == 0, N % 4 == 0, K % 16 == 0, A and B 16-byte aligned with
+ * lda % 4 == ldb % 4 == 0.  Form 2 sums K in slices of 512 rows, added in slice order (the weight gradient's scheme); with more
+ * than one slice the call takes a temporary buffer of the partial matrices from the device allocator and waits for `stream`. */
+int vinet_token_gemm(int32_t mma, int32_t form, int32_t epi, const float* A, int32_t lda, const float* B, int32_t ldb,
+                     float* C, int32_t ldc, int32_t M, int32_t N, int32_t K, const float* bias, const float* res, void* stream);
 /* split / mean / broadcast behind it (model.py:175-185).  x = tokens [B][Sv + n_audio][E], y [B][Sv positions][2E]:
  * y[b][pos][0:E] = x[b][pos], y[b][pos][E:2E] = mean over the n_audio last rows of x[b].  Backward writes (does not add)
  * dx: rows [0, Sv) = dy[..., 0:E]; each audio row = (1 / n_audio) * the sum of dy[..., E:2E] over positions in index order. */

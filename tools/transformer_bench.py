@@ -6,7 +6,9 @@
   tokens    the token-wise encoder of VideoAudioSaliencyFusionModel (3 layers, 339 tokens x 512 features, 4 heads) forward and
             forward + backward at --token_batches (default 1, 8, 32, 192) against eager nn.TransformerEncoder in fp32 on the same
             device, weights and input (dropout 0 on both), the two alternating inside each timed round; with the achieved share of
-            the 155 TF/s fp32-MFMA rate (FLOPs counted from the shapes) and the workspace bytes per clip
+            the 155 TF/s fp32-MFMA rate (FLOPs counted from the shapes) and the workspace bytes per clip.  --token_mma fp32,bf16x3,bf16
+            times the encoder in each of these arithmetic modes of its linear products (engine option TOKEN_MMA), all of them and
+            aten taking turns inside each round; the first mode fills the hip_* columns, the others hip_<mode>_* columns
   step      the AViNet training step (kldiv + fused Adam, --dtype) with and without use_transformer at --step_batches (default 1, 8, 32, 192)
 
 Warm-up, then the median of --repeats timed runs (device events around one call).  One JSON line per measurement on stdout.
@@ -135,19 +137,28 @@ def bench_tokens(args, dev):
     aten.load_state_dict({k[len("transformer_encoder."):]: v for k, v in sd.items() if k.startswith("transformer_encoder.")})
     pe = sd["pos_encoder.pe"].to(dev)
     flops = NL * token_layer_flops(S, Ef, Ef)
+    modes = [m for m in args.token_mma.split(",") if m]
     for B in [int(b) for b in args.token_batches.split(",")]:
         x = synth.normal("bench_tok_x", (B, Ef, S, 1, 1), 2).to(dev)          # NCDHW: position = token, channel = feature
         g = synth.normal("bench_tok_g", (B, Ef, S, 1, 1), 3).to(dev)
         xt = x.reshape(B, Ef, S).permute(2, 0, 1).contiguous()                  # [S, B, E] for nn.TransformerEncoder
         gt = g.reshape(B, Ef, S).permute(2, 0, 1).contiguous()
 
-        def hip_fwd():
-            with torch.no_grad():
-                return fusion.token_encoder_tokens(tf, x)
+        def hip_fwd(mode=modes[0]):
+            old = E.configure(token_mma=mode)
+            try:
+                with torch.no_grad():
+                    return fusion.token_encoder_tokens(tf, x)
+            finally:
+                E.configure(**old)
 
-        def hip_fb():
-            xr = x.detach().requires_grad_(True)
-            (fusion.token_encoder_tokens(tf, xr) * g).sum().backward()
+        def hip_fb(mode=modes[0]):
+            old = E.configure(token_mma=mode)
+            try:
+                xr = x.detach().requires_grad_(True)
+                (fusion.token_encoder_tokens(tf, xr) * g).sum().backward()
+            finally:
+                E.configure(**old)
 
         def aten_fwd():
             with torch.no_grad():
@@ -157,17 +168,28 @@ def bench_tokens(args, dev):
             xr = xt.detach().requires_grad_(True)
             (aten(xr + pe) * gt).sum().backward()
 
+        def col(mode, what):
+            return "hip_" + what if mode == modes[0] else "hip_%s_%s" % (mode, what)
+
         with torch.no_grad():
-            diff = float((fusion.token_encoder_tokens(tf, x).reshape(B, Ef, S).permute(2, 0, 1) - aten(xt + pe)).abs().max())
+            ref = aten(xt + pe)
+            diffs = {m: float((hip_fwd(m).reshape(B, Ef, S).permute(2, 0, 1) - ref).abs().max()) for m in modes}
         reps = max(5, args.repeats // (1 if B <= 32 else 3))
-        row = dict(bench="token_encoder", B=B, S=S, E=Ef, H=H, L=NL, max_abs_diff_to_aten=diff, repeats=reps)
-        t = alternating_ms(dict(hip_fwd=hip_fwd, aten_fwd=aten_fwd), args.warmup, reps)
-        t.update(alternating_ms(dict(hip_fwd_bwd=hip_fb, aten_fwd_bwd=aten_fb), args.warmup, reps))
+        row = dict(bench="token_encoder", B=B, S=S, E=Ef, H=H, L=NL, token_mma=modes, max_abs_diff_to_aten=diffs[modes[0]], repeats=reps)
+        for m in modes[1:]:
+            row["max_abs_diff_to_aten_" + m] = diffs[m]
+        fw = {col(m, "fwd"): (lambda m=m: hip_fwd(m)) for m in modes}
+        fb = {col(m, "fwd_bwd"): (lambda m=m: hip_fb(m)) for m in modes}
+        t = alternating_ms(dict(fw, aten_fwd=aten_fwd), args.warmup, reps)
+        t.update(alternating_ms(dict(fb, aten_fwd_bwd=aten_fb), args.warmup, reps))
         for name, (med, lo) in t.items():
             row[name + "_ms"] = round(med, 4)
             row[name + "_min_ms"] = round(lo, 4)
         row["aten_over_hip_fwd"] = round(row["aten_fwd_ms"] / row["hip_fwd_ms"], 3)
         row["aten_over_hip_fwd_bwd"] = round(row["aten_fwd_bwd_ms"] / row["hip_fwd_bwd_ms"], 3)
+        for m in modes[1:]:
+            row["aten_over_hip_%s_fwd" % m] = round(row["aten_fwd_ms"] / row[col(m, "fwd") + "_ms"], 3)
+            row["aten_over_hip_%s_fwd_bwd" % m] = round(row["aten_fwd_bwd_ms"] / row[col(m, "fwd_bwd") + "_ms"], 3)
         # whole-call rates (import / export of the NCDHW boundary and the host's launches included), not a kernel's share of peak
         row["hip_fwd_share_of_fp32_mfma_peak"] = round(B * flops / (row["hip_fwd_ms"] * 1e-3) / FP32_MFMA_PEAK, 4)
         row["hip_fwd_bwd_share_of_fp32_mfma_peak"] = round(3 * B * flops / (row["hip_fwd_bwd_ms"] * 1e-3) / FP32_MFMA_PEAK, 4)
@@ -229,6 +251,7 @@ def main():
     p.add_argument("--step_batches", default="1,8,32,192")
     p.add_argument("--encoder_batches", default="1,8,32,192")
     p.add_argument("--token_batches", default="1,8,32,192")
+    p.add_argument("--token_mma", default="fp32", help="tokens: comma list of fp32, bf16x3, bf16 (the encoder's linear arithmetic), timed side by side")
     p.add_argument("--dtype", default="bf16")
     args = p.parse_args()
     dev = torch.device("cuda:0")

@@ -16,6 +16,7 @@ F32, BF16 = 0, 1
 F32S = 2     # conv / weight-gradient descriptors: fp32 tensors, split-bf16 matrix arithmetic (include/vinet_hip.h)
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 CONV_GENERIC, CONV_STEM = 0, 1
+TK_MMA_F32, TK_MMA_BF16X3, TK_MMA_BF16 = 0, 1, 2     # VINET_TK_MMA_*: arithmetic of the token encoder's linear products
 ABI_VERSION = 16
 
 
@@ -139,6 +140,10 @@ SIGNATURES = {
     "vinet_token_encoder_workspace": [_PK],
     "vinet_token_encoder_fwd": [_PK, _PT, _PT, _vp],
     "vinet_token_encoder_bwd": [_PK, _PT, _PT, _vp],
+    "vinet_token_encoder_workspace_mma": [_PK, _i32],
+    "vinet_token_encoder_fwd_mma": [_PK, _i32, _PT, _PT, _vp],
+    "vinet_token_encoder_bwd_mma": [_PK, _i32, _PT, _PT, _vp],
+    "vinet_token_gemm": [_i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "vinet_token_split_fwd": [_PT, _i32, _i32, _PT, _vp],
     "vinet_token_split_bwd": [_PT, _i32, _i32, _PT, _vp],
     "vinet_resize_blur": [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp],
@@ -161,7 +166,8 @@ SIGNATURES = {
 _RESTYPE = {"vinet_last_error": C.c_char_p, "vinet_conv3d_splitk_bytes": C.c_int64, "vinet_frames_preprocess_ws_bytes": C.c_int64,
             "vinet_gt_preprocess_ws_bytes": C.c_int64, "vinet_auc_judd_workspace": C.c_size_t, "vinet_auc_shuffled_workspace": C.c_size_t, "vinet_auc_borji_workspace": C.c_size_t,
             "vinet_emd_workspace": C.c_size_t,
-            "vinet_transformer_workspace": C.c_int64, "vinet_token_encoder_workspace": C.c_int64}
+            "vinet_transformer_workspace": C.c_int64, "vinet_token_encoder_workspace": C.c_int64,
+            "vinet_token_encoder_workspace_mma": C.c_int64}
 
 _LIB = None
 _TEST_DOUBLE = None

@@ -5,6 +5,8 @@
 // view's rows (+ pe) into the fp32 token matrix, the last one copies them out.  In the workspace every clip owns Sp = S rounded up
 // to 16 rows, so the token matrices [M = B Sp][.] meet the token GEMM's contract (M % 4 == 0, a weight gradient's reduction axis
 // a multiple of 16) whatever S and B are, and the stages between attention are the ones of transformer.hip (tf_common.h).
+// The linear products (the six linears of a layer, their data and weight gradients) run in the arithmetic the caller names
+// (VINET_TK_MMA_*): tf_gemm on the fp32 MFMA, or tk_gemm_bf16.h on the bf16 MFMA over the same fp32 matrices.
 // Padding rows: ZERO in the encoder's input and in every gradient matrix, finite (a bias, a LayerNorm of it) in every saved
 // activation, so they add exactly 0 to each weight and bias gradient; attention never reads them as keys and writes zeros for them.
 //
@@ -16,6 +18,7 @@
 // Dropout: the keep masks of tf_common.h; sites 1..3 are indexed by the PADDED row (forward and backward agree, the export kernel
 // maps them to [B S][.]), site 0 by the unpadded [B][H][S][S] index.
 #include "tf_common.h"
+#include "tk_gemm_bf16.h"
 
 namespace {
 
@@ -453,6 +456,12 @@ static bool tensor_ok(const VinetTensor* t, const VinetTokenEncoderDesc* d) {
   return t && t->ptr && t->B == d->B && (long)t->T * t->H * t->W == d->S && t->C == d->E && t->ld >= t->C;
 }
 
+static int check_mma(int32_t mma, const char* who) {
+  VN_CHECK_ARG(mma == VINET_TK_MMA_F32 || mma == VINET_TK_MMA_BF16X3 || mma == VINET_TK_MMA_BF16,
+               "%s: mma = %d is not VINET_TK_MMA_F32 (0), _BF16X3 (1) or _BF16 (2)", who, mma);
+  return 0;
+}
+
 #define TK_BY_WIDTH(D, CALL)                 \
   do {                                       \
     if ((D) <= 16) { CALL(1); }              \
@@ -463,10 +472,12 @@ static bool tensor_ok(const VinetTensor* t, const VinetTokenEncoderDesc* d) {
 
 }  // namespace
 
-extern "C" int64_t vinet_token_encoder_workspace(const VinetTokenEncoderDesc* d) {
-  if (check_desc(d, "token_encoder_workspace")) return -1;
+// (the bf16 GEMMs read and write the fp32 matrices of the fp32 ones: one layout, one size, whatever the mode)
+extern "C" int64_t vinet_token_encoder_workspace_mma(const VinetTokenEncoderDesc* d, int32_t mma) {
+  if (check_desc(d, "token_encoder_workspace") || check_mma(mma, "token_encoder_workspace")) return -1;
   return make_layout(d).total * (int64_t)sizeof(float);
 }
+extern "C" int64_t vinet_token_encoder_workspace(const VinetTokenEncoderDesc* d) { return vinet_token_encoder_workspace_mma(d, VINET_TK_MMA_F32); }
 
 // mask export layout (bytes): per layer [site 0: B H S S | site 1: B S E | site 2: B S F | site 3: B S E]
 static inline long tk_mask_layer_bytes(const VinetTokenEncoderDesc* d) {
@@ -474,8 +485,8 @@ static inline long tk_mask_layer_bytes(const VinetTokenEncoderDesc* d) {
   return (long)d->B * d->H * d->S * d->S + 2 * MS * d->E + MS * d->F;
 }
 
-extern "C" int vinet_token_encoder_fwd(const VinetTokenEncoderDesc* d, const VinetTensor* x, const VinetTensor* y, void* stream) {
-  if (check_desc(d, "token_encoder_fwd")) return -1;
+extern "C" int vinet_token_encoder_fwd_mma(const VinetTokenEncoderDesc* d, int32_t mma, const VinetTensor* x, const VinetTensor* y, void* stream) {
+  if (check_desc(d, "token_encoder_fwd") || check_mma(mma, "token_encoder_fwd")) return -1;
   VN_CHECK_ARG(tensor_ok(x, d) && tensor_ok(y, d), "token_encoder_fwd: x / y must be [B][T H W = S][C = E] channels-last with ld >= C");
   VN_CHECK_ARG(d->params && d->pe && d->ws && (((uintptr_t)d->ws) & 15) == 0, "token_encoder_fwd: params, pe and a 16-byte aligned workspace are required");
   const Layout L = make_layout(d);
@@ -503,17 +514,17 @@ extern "C" int vinet_token_encoder_fwd(const VinetTokenEncoderDesc* d, const Vin
     // (eval mode has ONE slot; the layer's input is then `out`, which this layer's last LayerNorm overwrites after its readers)
     const float* xin = cur;
     ep.bias = P[P_INB]; ep.res = nullptr; ep.stream = 0;
-    tf_gemm_launch<true, true, EPI_BIAS>(s, xin, E, P[P_INW], E, sv + L.qkv, 3 * E, M, 3 * E, E, ep);
+    tk_gemm_launch<true, true, EPI_BIAS>(mma, s, xin, E, P[P_INW], E, sv + L.qkv, 3 * E, M, 3 * E, E, ep);
 #define TK_FWD(DT) hipLaunchKernelGGL(tk_attn_fwd<DT>, agrid, dim3(256), 0, s, sv + L.qkv, S, Sp, E, H, D, qscale, sv + L.P, sv + L.ao, drop, 4 * l + 0, mk)
     TK_BY_WIDTH(D, TK_FWD);
 #undef TK_FWD
     ep.bias = P[P_OUTB]; ep.res = xin; ep.stream = 4 * l + 1;
-    tf_gemm_launch<true, true, EPI_BIAS_DROP_RES>(s, sv + L.ao, E, P[P_OUTW], E, sv + L.z1, E, M, E, E, ep);
+    tk_gemm_launch<true, true, EPI_BIAS_DROP_RES>(mma, s, sv + L.ao, E, P[P_OUTW], E, sv + L.z1, E, M, E, E, ep);
     hipLaunchKernelGGL(tf_ln_fwd<8>, dim3(vn_div_up(M, 4)), dim3(256), 0, s, sv + L.z1, P[P_N1W], P[P_N1B], M, E, d->eps, sv + L.x1, sv + L.st1);
     ep.bias = P[P_L1B]; ep.res = nullptr; ep.stream = 4 * l + 2;
-    tf_gemm_launch<true, true, EPI_BIAS_RELU_DROP>(s, sv + L.x1, E, P[P_L1W], E, sv + L.hd, F, M, F, E, ep);
+    tk_gemm_launch<true, true, EPI_BIAS_RELU_DROP>(mma, s, sv + L.x1, E, P[P_L1W], E, sv + L.hd, F, M, F, E, ep);
     ep.bias = P[P_L2B]; ep.res = sv + L.x1; ep.stream = 4 * l + 3;
-    tf_gemm_launch<true, true, EPI_BIAS_DROP_RES>(s, sv + L.hd, F, P[P_L2W], F, sv + L.z2, E, M, E, F, ep);
+    tk_gemm_launch<true, true, EPI_BIAS_DROP_RES>(mma, s, sv + L.hd, F, P[P_L2W], F, sv + L.z2, E, M, E, F, ep);
     float* nxt = (d->train && l + 1 < d->L) ? ws + (l + 1) * L.per_layer + L.xin : ws + L.out;
     hipLaunchKernelGGL(tf_ln_fwd<8>, dim3(vn_div_up(M, 4)), dim3(256), 0, s, sv + L.z2, P[P_N2W], P[P_N2B], M, E, d->eps, nxt, sv + L.st2);
     cur = nxt;
@@ -531,8 +542,8 @@ extern "C" int vinet_token_encoder_fwd(const VinetTokenEncoderDesc* d, const Vin
   return vn_launch_status("token_encoder_fwd");
 }
 
-extern "C" int vinet_token_encoder_bwd(const VinetTokenEncoderDesc* d, const VinetTensor* dy, const VinetTensor* dx, void* stream) {
-  if (check_desc(d, "token_encoder_bwd")) return -1;
+extern "C" int vinet_token_encoder_bwd_mma(const VinetTokenEncoderDesc* d, int32_t mma, const VinetTensor* dy, const VinetTensor* dx, void* stream) {
+  if (check_desc(d, "token_encoder_bwd") || check_mma(mma, "token_encoder_bwd")) return -1;
   VN_CHECK_ARG(d->train, "token_encoder_bwd: the forward pass must have run with train = 1 (it saves the layers' state)");
   VN_CHECK_ARG(tensor_ok(dy, d) && (!dx || tensor_ok(dx, d)), "token_encoder_bwd: dy / dx must be [B][T H W = S][C = E] channels-last with ld >= C");
   VN_CHECK_ARG(d->params && d->grads && d->ws && (((uintptr_t)d->ws) & 15) == 0, "token_encoder_bwd: params, grads and the forward's workspace are required");
@@ -565,19 +576,19 @@ extern "C" int vinet_token_encoder_bwd(const VinetTokenEncoderDesc* d, const Vin
     hipLaunchKernelGGL((tf_ln_bwd<8, TK_GROUP / 4>), dim3(NG), dim3(256), 0, s, dOut, sv + L.z2, sv + L.st2, P[P_N2W], E, dZ, dZm, part, ps, oL2B, oN2W, oN2B, drop, 4 * l + 3);
     // linear2: dH = (dZm W2) under the ReLU / dropout of the hidden;  dW2 += dZm^T hidden
     ep.res = sv + L.hd;
-    tf_gemm_launch<true, false, EPI_RELU_MASK>(s, dZm, E, P[P_L2W], F, dH, F, M, F, E, ep);
-    if (G[P_L2W]) tf_wgrad_launch(s, ns, wpart, dZm, E, sv + L.hd, F, G[P_L2W], E, F, M);
+    tk_gemm_launch<true, false, EPI_RELU_MASK>(mma, s, dZm, E, P[P_L2W], F, dH, F, M, F, E, ep);
+    if (G[P_L2W]) tk_wgrad_launch(mma, s, ns, wpart, dZm, E, sv + L.hd, F, G[P_L2W], E, F, M);
     hipLaunchKernelGGL(tf_colsum_clip<TK_GROUP>, dim3(vn_div_up(F, 256), NG), dim3(256), 0, s, dH, F, part, ps, oL1B);
     // linear1: dX1 = dH W1 + dZ;  dW1 += dH^T x1
     ep.res = dZ;
-    tf_gemm_launch<true, false, EPI_ADD_RES>(s, dH, F, P[P_L1W], E, dX1, E, M, E, F, ep);
-    if (G[P_L1W]) tf_wgrad_launch(s, ns, wpart, dH, F, sv + L.x1, E, G[P_L1W], F, E, M);
+    tk_gemm_launch<true, false, EPI_ADD_RES>(mma, s, dH, F, P[P_L1W], E, dX1, E, M, E, F, ep);
+    if (G[P_L1W]) tk_wgrad_launch(mma, s, ns, wpart, dH, F, sv + L.x1, E, G[P_L1W], F, E, M);
     // LayerNorm 1
     hipLaunchKernelGGL((tf_ln_bwd<8, TK_GROUP / 4>), dim3(NG), dim3(256), 0, s, dX1, sv + L.z1, sv + L.st1, P[P_N1W], E, dZ, dZm, part, ps, oOUTB, oN1W, oN1B, drop, 4 * l + 1);
     // attention projection: dAO = dZm Wo (into dH's buffer);  dWo += dZm^T ao
     float* dAO = dH;
-    tf_gemm_launch<true, false, EPI_PLAIN>(s, dZm, E, P[P_OUTW], E, dAO, E, M, E, E, ep);
-    if (G[P_OUTW]) tf_wgrad_launch(s, ns, wpart, dZm, E, sv + L.ao, E, G[P_OUTW], E, E, M);
+    tk_gemm_launch<true, false, EPI_PLAIN>(mma, s, dZm, E, P[P_OUTW], E, dAO, E, M, E, E, ep);
+    if (G[P_OUTW]) tk_wgrad_launch(mma, s, ns, wpart, dZm, E, sv + L.ao, E, G[P_OUTW], E, E, M);
     hipLaunchKernelGGL(tk_attn_dot, dim3(vn_div_up((long)M * H, 256)), dim3(256), 0, s, dAO, sv + L.ao, (long)M * H, E, H, D, dot);
 #define TK_BWD(DT)                                                                                                                                    \
   hipLaunchKernelGGL(tk_attn_bwd_q<DT>, agrid, dim3(256), 0, s, sv + L.qkv, sv + L.P, dAO, dot, S, Sp, E, H, D, qscale, dQKV, drop, 4 * l + 0);   \
@@ -587,8 +598,8 @@ extern "C" int vinet_token_encoder_bwd(const VinetTokenEncoderDesc* d, const Vin
     hipLaunchKernelGGL(tf_colsum_clip<TK_GROUP>, dim3(vn_div_up(3 * E, 256), NG), dim3(256), 0, s, dQKV, 3 * E, part, ps, oINB);
     // QKV projection: dXin = dQKV Win + dZ;  dWin += dQKV^T xin
     ep.res = dZ;
-    tf_gemm_launch<true, false, EPI_ADD_RES>(s, dQKV, 3 * E, P[P_INW], E, dOut, E, M, E, 3 * E, ep);
-    if (G[P_INW]) tf_wgrad_launch(s, ns, wpart, dQKV, 3 * E, sv + L.xin, E, G[P_INW], 3 * E, E, M);
+    tk_gemm_launch<true, false, EPI_ADD_RES>(mma, s, dQKV, 3 * E, P[P_INW], E, dOut, E, M, E, 3 * E, ep);
+    if (G[P_INW]) tk_wgrad_launch(mma, s, ns, wpart, dQKV, 3 * E, sv + L.xin, E, G[P_INW], 3 * E, E, M);
     SmallGrads sg;
     const int pidx[8] = {P_INB, P_OUTB, P_L1B, P_L2B, P_N1W, P_N1B, P_N2W, P_N2B};
     const int offs[9] = {oINB, oOUTB, oL1B, oL2B, oN1W, oN1B, oN2W, oN2B, ps};
@@ -601,6 +612,77 @@ extern "C" int vinet_token_encoder_bwd(const VinetTokenEncoderDesc* d, const Vin
     else hipLaunchKernelGGL(tk_store_tokens<float>, sgrid, dim3(256), 0, s, dOut, S, Sp, E, (float*)dx->ptr, (long)dx->sB, dx->ld);
   }
   return vn_launch_status("token_encoder_bwd");
+}
+
+extern "C" int vinet_token_encoder_fwd(const VinetTokenEncoderDesc* d, const VinetTensor* x, const VinetTensor* y, void* stream) {
+  return vinet_token_encoder_fwd_mma(d, VINET_TK_MMA_F32, x, y, stream);
+}
+extern "C" int vinet_token_encoder_bwd(const VinetTokenEncoderDesc* d, const VinetTensor* dy, const VinetTensor* dx, void* stream) {
+  return vinet_token_encoder_bwd_mma(d, VINET_TK_MMA_F32, dy, dx, stream);
+}
+
+// ---- one product (vinet_token_gemm) -------------------------------------------------------------------------------------------
+namespace {
+struct TkGemmArgs {
+  int mma;
+  const float *A, *B;
+  float* C;
+  int lda, ldb, ldc, M, N, K;
+  GemmEpi ep;
+};
+
+template <bool AK, bool BK, int EPI>
+static int tk_one_product(const TkGemmArgs& g, hipStream_t s) {
+  const int nsplit = (!AK && g.K > TF_WGRAD_CHUNK) ? (g.K + TF_WGRAD_CHUNK - 1) / TF_WGRAD_CHUNK : 1;
+  if (nsplit <= 1) {
+    tk_gemm_launch<AK, BK, EPI>(g.mma, s, g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.M, g.N, g.K, g.ep);
+    return vn_launch_status("token_gemm");
+  }
+  float* part = nullptr;
+  const hipError_t e = hipMalloc((void**)&part, (size_t)nsplit * g.M * g.N * sizeof(float));
+  VN_CHECK_ARG(e == hipSuccess, "token_gemm: no memory for %d partial matrices of %d x %d: %s", nsplit, g.M, g.N, hipGetErrorString(e));
+  tk_wgrad_slices(g.mma, s, nsplit, part, g.A, g.lda, g.B, g.ldb, g.M, g.N, g.K);
+  hipLaunchKernelGGL(tk_reduce_epi<EPI>, dim3(vn_div_up((long)g.M * g.N, 256)), dim3(256), 0, s, part, nsplit, g.M, g.N, g.C, g.ldc, g.ep);
+  const int rc = vn_launch_status("token_gemm");
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(part);
+  return rc;
+}
+
+template <bool AK, bool BK>
+static int tk_one_product_epi(int epi, const TkGemmArgs& g, hipStream_t s) {
+  switch (epi) {
+    case 0: return tk_one_product<AK, BK, EPI_PLAIN>(g, s);
+    case 1: return tk_one_product<AK, BK, EPI_BIAS>(g, s);
+    case 2: return tk_one_product<AK, BK, EPI_BIAS_RELU_DROP>(g, s);     // (no dropout: ep.drop.thr == 0)
+    case 3: return tk_one_product<AK, BK, EPI_ADD_RES>(g, s);
+    default: return tk_one_product<AK, BK, EPI_ACCUM>(g, s);
+  }
+}
+}  // namespace
+
+extern "C" int vinet_token_gemm(int32_t mma, int32_t form, int32_t epi, const float* A, int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc,
+                                int32_t M, int32_t N, int32_t K, const float* bias, const float* res, void* stream) {
+  if (check_mma(mma, "token_gemm")) return -1;
+  VN_CHECK_ARG(form >= 0 && form <= 2, "token_gemm: form = %d is not 0 (A[m][k] B[n][k]), 1 (A[m][k] B[k][n]) or 2 (A[k][m] B[k][n])", form);
+  VN_CHECK_ARG(epi >= 0 && epi <= 4, "token_gemm: epi = %d is not 0 (plain), 1 (+ bias), 2 (relu(. + bias)), 3 (+ res) or 4 (C +=)", epi);
+  VN_CHECK_ARG(M > 0 && M % 4 == 0, "token_gemm: M = %d must be a positive multiple of 4", M);
+  VN_CHECK_ARG(N > 0 && N % 4 == 0, "token_gemm: N = %d must be a positive multiple of 4", N);
+  VN_CHECK_ARG(K > 0 && K % 16 == 0, "token_gemm: K = %d must be a positive multiple of 16", K);
+  VN_CHECK_ARG(A && B && C, "token_gemm: null matrix");
+  const int wa = form == 2 ? M : K, wb = form == 0 ? K : N;
+  VN_CHECK_ARG(lda >= wa && ldb >= wb && ldc >= N, "token_gemm: row strides lda = %d, ldb = %d, ldc = %d are below the widths %d, %d, %d", lda, ldb, ldc, wa, wb, N);
+  VN_CHECK_ARG(lda % 4 == 0 && ldb % 4 == 0 && (((uintptr_t)A | (uintptr_t)B) & 15) == 0, "token_gemm: rows of A and B must be 16-byte aligned (lda = %d, ldb = %d)", lda, ldb);
+  VN_CHECK_ARG((epi != 1 && epi != 2) || bias, "token_gemm: epi = %d needs bias", epi);
+  VN_CHECK_ARG(epi != 3 || res, "token_gemm: epi = 3 needs res");
+  TkGemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.mma = mma; g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+  g.ep.bias = bias; g.ep.res = res; g.ep.drop = tf_make_drop(0.f, 0, nullptr);
+  hipStream_t s = (hipStream_t)stream;
+  if (form == 0) return tk_one_product_epi<true, true>(epi, g, s);
+  if (form == 1) return tk_one_product_epi<true, false>(epi, g, s);
+  return tk_one_product_epi<false, false>(epi, g, s);
 }
 
 static int split_args_ok(const VinetTensor* x, const VinetTensor* y, int32_t n_audio, const char* who) {

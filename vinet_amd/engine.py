@@ -107,6 +107,10 @@ _CONFIG = dict(
     # (profiles/pool_keep_*).  0 = the copies.
     POOL_KEEPS_SKIP=1,
     PARAM_GRAD_MODE="fused",    # see set_param_grad_mode
+    # arithmetic of the token encoder's linear products (include/vinet_hip.h, VINET_TK_MMA_*): "fp32" (exact products on the fp32
+    # MFMA, what the encoder has always run), "bf16x3" (split bf16, the arithmetic of the fp32s convs), "bf16", or "match": the
+    # context's own -- fp32 -> fp32, fp32s -> bf16x3, bf16 -> bf16.  Attention, softmax and LayerNorm are fp32 in every mode.
+    TOKEN_MMA="fp32",
     # Schedule stress (tests): shader clocks a spin kernel idles on the weight-gradient stream in front of every weight-gradient
     # launch (DBG_SPIN_SIDE) / on the main stream in front of every data gradient (DBG_SPIN_MAIN) / on a branch stream each time
     # a fork enters it (DBG_SPIN_FORK; negative: on the forking stream instead, so the branch streams run ahead).  A result
@@ -139,6 +143,8 @@ def configure(**kw):
             v = int(v)
         elif isinstance(d, str):
             v = str(v)
+        if K == "TOKEN_MMA" and v not in TOKEN_MMA_VALUES:
+            raise ValueError("engine.configure: token_mma = %r is not one of %s" % (v, ", ".join(TOKEN_MMA_VALUES)))
         old[K] = globals()[K]
         globals()[K] = v
         if K == "PARAM_GRAD_MODE":
@@ -150,6 +156,17 @@ def configure(**kw):
             if _ABLATE_TAGS:
                 _ABLATE.add("\0tags")
     return old
+
+
+TOKEN_MMA_VALUES = ("fp32", "bf16x3", "bf16", "match")
+
+
+def token_mma_mode(dt):
+    """the VINET_TK_MMA_* value of the TOKEN_MMA option in a context whose compute dtype (Ctx.cdt) is `dt`: L.F32 / L.F32S / L.BF16"""
+    name = TOKEN_MMA
+    if name == "match":
+        name = {L.F32: "fp32", L.F32S: "bf16x3", L.BF16: "bf16"}[dt]
+    return {"fp32": L.TK_MMA_F32, "bf16x3": L.TK_MMA_BF16X3, "bf16": L.TK_MMA_BF16}[name]
 
 
 def configure_from_string(text):
