@@ -701,7 +701,7 @@ int vinet_gt_preprocess(const uint8_t* src, int32_t N, int32_t H, int32_t W, flo
 /* misc */
 /* Tuning / A-B switches (process-wide), `name` (default): meaning.  The list is vinet_amd/csrc/options.h, the one table the
  * library defines its switches from.  None of them changes results beyond floating-point accumulation order.
- * Returns 0; -1 for an unknown name; -2 for a value that needs a -DVINET_EXPERIMENTS build of the library.
+ * Returns 0; -1 for an unknown name.
  *   "dma" (1): LDS-DMA conv kernel (conv_dma) where legal; 0 = the register-staged kernel
  *   "dma3" (1): LDS-DMA kernel for the split-bf16 form (conv_dma3); 0 = the register-staged kernel
  *   "pp" (1): 256x256x64 ping-pong conv kernel: 0 off, 1 heuristic, 2 force, 3 / 4 force the 256- / 192-wide shape
@@ -729,8 +729,6 @@ int vinet_gt_preprocess(const uint8_t* src, int32_t N, int32_t H, int32_t W, flo
  *   "n128_kmax" (64): 128-wide outputs: 128-row tiles up to this many K steps of 32 (0 = never)
  *   "n192_tile" (1): 128x192 tiles for N % 192 == 0 instead of 256x96: 0 off, 1 heuristic, 2 also on small grids (tests)
  *   "tperm" (0): t-fastest M-tile order (L2 reuse across temporal taps): 1 on
- *   "epi_rows" (0): conv epilogue stores whole rows through a wave-private LDS image: 1 on (-DVINET_EXPERIMENTS builds
- *       only)
  *   "bnb_epi" (1): BatchNorm-backward partial sums out of the shared conv epilogue; 0 = only the fused temporal data
  *       gradient
  *   "wgrad_dma" (1): LDS-DMA multi-tap weight-gradient kernel where legal; 0 = the register-staged kernel
@@ -748,8 +746,8 @@ int vinet_gt_preprocess(const uint8_t* src, int32_t N, int32_t H, int32_t W, flo
  *   "wgrad_tf" (1): temporal-tap weight gradient (wgrad_tf): 0 off, 1 heuristic, 2 every eligible shape (tests)
  *   "wgrad_skinny" (1): weight gradient of pointwise convs with 8 output channels: 0 off, 1 heuristic, 2 every eligible
  *       shape (tests)
- *   "bn_lean" (1): register-lean bf16 BatchNorm-backward kernels: 0 = the generic 8-channel forms, 2 = a
- *       -DVINET_EXPERIMENTS variant
+ *   "bn_lean" (1): register-lean bf16 BatchNorm-backward kernels: 0 = the generic 8-channel forms, 1 =
+ *       register-lean
  *   "bn_rows" (1024): cap on the workgroups (= partial rows) of a channel reduction (clamped to >= 1)
  *   "reduce_il" (1): channel reductions: blocks interleave rounds over one window; 0 = one contiguous range per block
  *   "reduce_small" (1): tensors of <= 64 voxels take channel_reduce_small_kernel; 0 off

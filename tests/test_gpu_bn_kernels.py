@@ -23,7 +23,7 @@ asserted cell by cell in the host test):
   bn_bwd_apply8_kernel<float, true>        the fp32 seam and views cases marked -split (dx against vinet_bn_bwd_apply's, hi / lo planes)
   bn_bwd_apply_kernel<T>                   elementwise (C = 4, 12: 255 ... 258 quads), dx_off_grid, views with C = 12.  Never launched by
                                            a kernel test before.
-  (act_bwd_kernel: tests/test_gpu_tail_kernels.py.  The VINET_EXPERIMENTS instantiations <2, 6> are not built.)
+  (act_bwd_kernel: tests/test_gpu_tail_kernels.py.  <4, 4> is the only instantiation of the two bf16 kernels the library launches.)
 
 NOT COVERED: the doubling of the apply kernels' voxels per block past 16 384 blocks, which needs about 1 GB of tensors.  The refused
 forms (a scale without a shift, ragged group loops) are asked for their return value only, never launched."""

@@ -418,7 +418,6 @@ OPTION_ROWS = {
                                                  (("o_tperm_wpp_3t", (2, 5, 8, 8), 96, 128) + T3 + (True, {}), BF16, None, dict(wgrad_pp=3)),
                                                  (_wcase(K.WGRAD_PP_CASES, "pp_bigm"), BF16, None, dict(wgrad_pp=0)), (_wcase(K.WGRAD_CASES, "splitk"), BF16, None, dict(wgrad_pp=0))],
                     LADDER, None),
-    "epi_rows": _exempt("needs a -DVINET_EXPERIMENTS build (test_conv3d_whole_row_epilogue runs it there)", "test_conv3d_whole_row_epilogue"),
     "bnb_epi": dict(kind="custom", test="test_option_bnb_epi_off_refuses_the_launch"),
     "wgrad_dma": _sweep("wgrad_dma", [0], _bf(*K.WGRAD_CASES), {}, "name"),
     "wgrad_tg": _exempt("swept: every (tile, taps per group) of the launch table", "test_wgrad_ledger"),
@@ -433,7 +432,7 @@ OPTION_ROWS = {
     "wgrad_rs4": _sweep("wgrad_rs4", [0], _bf(*[_wcase(K.WGRAD_RS_CASES, n, tline=4) for n in RS_48]), dict(wgrad_rs=2), "name"),
     "wgrad_tf": _exempt("swept", "test_conv3d_wgrad_tframes"),
     "wgrad_skinny": _exempt("swept", "test_conv3d_wgrad_skinny"),
-    "bn_lean": dict(kind="custom", test="test_option_bn_reductions", values=[0], note="2 needs a -DVINET_EXPERIMENTS build"),
+    "bn_lean": dict(kind="custom", test="test_option_bn_reductions", values=[0]),
     "bn_rows": dict(kind="custom", test="test_option_bn_reductions", values=[1, 7]),
     "reduce_il": dict(kind="custom", test="test_option_bn_reductions", values=[0]),
     "reduce_small": dict(kind="custom", test="test_option_bn_reductions", values=[0]),

@@ -183,6 +183,29 @@ def test_product_path_refuses_cpu_without_library_double():
         L._install_test_double(AbiEmulator())
 
 
+RETIRED_OPTIONS = ["WGRAD_CUS_DEC", "TAIL_WGRAD_FULL", "WGRAD_GROUP", "N_SIDE_STREAMS", "PERSISTENT_DW", "SPLIT_WGRAD_BF16", "SPLIT_IN_APPLY",
+                   "DEFER_DECODER_WGRAD_F32S", "BRANCH_STREAMS_SWAP", "STEM_FOLD"]
+
+
+@pytest.mark.parametrize("name", RETIRED_OPTIONS)
+def test_retired_engine_options_are_unknown(name):
+    """the decided A/B switches are gone: configure() and --cfg refuse their names like any other unknown option"""
+    with pytest.raises(KeyError):
+        E.configure(**{name: 1})
+    with pytest.raises(KeyError):
+        E.configure_from_string("%s=1" % name.lower())
+    assert name not in E.config() and name not in E._CONFIG and not hasattr(E, name)
+
+
+def test_engine_option_table_and_library_options_through_cfg():
+    assert len(E._CONFIG) == 25 and set(E.config()) == set(E._CONFIG)
+    try:
+        assert E.configure_from_string("lib.bn_lean=0") == {}
+        assert E.config()["lib"]["bn_lean"] == 0
+    finally:
+        L.LIB_OPTIONS.pop("bn_lean", None)
+
+
 def test_postprocess_host_api_follows_process_and_validate():
     """vinet_amd.utils.resize_blur / to_uint8 / postprocess / blur and the harness's out_size path against the
     oracle's statement of generate_result.py:95-104 (through the ABI emulator: host logic only)"""

@@ -25,13 +25,6 @@ static const struct { const char* name; int* value; } g_vinet_options[] = {VN_OP
 extern "C" int vinet_set_option(const char* name, int32_t value) {
   for (const auto& o : g_vinet_options) {
     if (!name || strcmp(name, o.name)) continue;
-#ifndef VINET_EXPERIMENTS
-    // measured-slower variants live in side builds only (python -c "from vinet_amd import build; build.build_variant('exp', ['-DVINET_EXPERIMENTS'])")
-    if ((o.value == &g_vinet_opt_epi_rows && value) || (o.value == &g_vinet_opt_bn_lean && value == 2)) {
-      vinet_set_error("set_option: %s=%d needs a -DVINET_EXPERIMENTS build of the library", name, value);
-      return -2;
-    }
-#endif
     *o.value = (o.value == &g_vinet_opt_bn_rows && value < 1) ? 1 : value;
     return 0;
   }
@@ -413,8 +406,6 @@ static int fill_args(const VinetConvDesc* d, ConvArgs& a, ConvRoute& r) {
                 d->y.T == d->oT && d->y.H == d->oH && d->y.W == d->oW &&
                 d->y.sB == (int64_t)d->y.T * d->y.H * d->y.W * d->y.ld) ? 1 : 0;
   a.act = d->act; a.accumulate = d->accumulate; a.out_f32 = d->out_dtype == VINET_F32;
-  // epi_rows: whole-row stores through a wave-private LDS image.  Measured (tools/conv_ab.py --opt epi_rows=0,1, profiles/r3_epi_rows_ab.txt): neutral on conv_dma, 1...7 % slower on the halo-tile kernels, whole step 306.5 -> 307.4 ms: off.  (The pointwise kernel, conv_pw.h, always stores whole rows: there it is worth 2x.)
-  a.epi_rows = g_vinet_opt_epi_rows;
   const int oeb = a.out_f32 ? 4 : 2;
   a.vec_ok = (a.N % 4 == 0) && (a.ldy % 4 == 0) && (a.sBy % 4 == 0) && ((((uintptr_t)d->y.ptr) % (4 * oeb)) == 0);
   r = vinet_conv_route(d, false);

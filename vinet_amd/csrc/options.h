@@ -28,7 +28,6 @@
   VN_OPT(n128_kmax,    64, "128-wide outputs: 128-row tiles up to this many K steps of 32 (0 = never)") \
   VN_OPT(n192_tile,    1, "128x192 tiles for N % 192 == 0 instead of 256x96: 0 off, 1 heuristic, 2 also on small grids (tests)") \
   VN_OPT(tperm,        0, "t-fastest M-tile order (L2 reuse across temporal taps): 1 on") \
-  VN_OPT(epi_rows,     0, "conv epilogue stores whole rows through a wave-private LDS image: 1 on (-DVINET_EXPERIMENTS builds only)") \
   VN_OPT(bnb_epi,      1, "BatchNorm-backward partial sums out of the shared conv epilogue; 0 = only the fused temporal data gradient") \
   VN_OPT(wgrad_dma,    1, "LDS-DMA multi-tap weight-gradient kernel where legal; 0 = the register-staged kernel") \
   VN_OPT(wgrad_tg,     0, "tuning: taps per group in the LDS-DMA weight gradient (0 = heuristic)") \
@@ -42,7 +41,7 @@
   VN_OPT(wgrad_rs4,    1, "row-streaming weight gradient: the four-wave form for W = 24, 48, 32, 64, 96; 0 = the eight-wave kernels") \
   VN_OPT(wgrad_tf,     1, "temporal-tap weight gradient (wgrad_tf): 0 off, 1 heuristic, 2 every eligible shape (tests)") \
   VN_OPT(wgrad_skinny, 1, "weight gradient of pointwise convs with 8 output channels: 0 off, 1 heuristic, 2 every eligible shape (tests)") \
-  VN_OPT(bn_lean,      1, "register-lean bf16 BatchNorm-backward kernels: 0 = the generic 8-channel forms, 2 = a -DVINET_EXPERIMENTS variant") \
+  VN_OPT(bn_lean,      1, "register-lean bf16 BatchNorm-backward kernels: 0 = the generic 8-channel forms, 1 = register-lean") \
   VN_OPT(bn_rows,      1024, "cap on the workgroups (= partial rows) of a channel reduction (clamped to >= 1)") \
   VN_OPT(reduce_il,    1, "channel reductions: blocks interleave rounds over one window; 0 = one contiguous range per block") \
   VN_OPT(reduce_small, 1, "tensors of <= 64 voxels take channel_reduce_small_kernel; 0 off") \

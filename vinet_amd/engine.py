@@ -53,16 +53,12 @@ _CONFIG = dict(
     # CUs the persistent weight-gradient kernels may occupy while they run beside the main stream (VinetWgradDesc::max_cus,
     # per launch); without a second stream they are alone on the GPU and get all of it
     WGRAD_CUS=208,
-    WGRAD_CUS_DEC=208,          # ... the decoder's (BatchNorm-less, deferred) weight gradients
-    TAIL_WGRAD_FULL=True,       # the tape's last weight gradient (the RGB stem) takes the whole chip
-    # weight-gradient jobs per join with the main stream (1 = a join per job), eager / under capture.  Replayed step: 1: 381 / 546
+    # weight-gradient jobs per join with the main stream under capture (eager: a join per job).  Replayed step: 1: 381 / 546
     # clips/s at 8 / 32 clips, 16: 410 / 583, 64: 367 / 549 -- every fork costs the replay ~12 us (profiles/r4_experiments.txt)
-    WGRAD_GROUP=1,
     WGRAD_GROUP_CAPTURE=16,
     # every packed weight gradient of a backward pass unpacked by ONE launch at its end (0 = one vinet_unpack_wgrad per conv).
     # Not used while a parameter-gradient hook is installed (the bucketed all-reduce wants each gradient as soon as it is final).
     MULTI_UNPACK=1,
-    N_SIDE_STREAMS=1,           # weight-gradient streams the jobs are dealt over round robin
     # Inference at small batches: the four branches of an Inception stage are independent kernels whose grids cannot fill 256
     # CUs (batch 1: 3 .. 170 workgroups), so below this many input voxels a stage forks them over two more streams and joins at
     # the concat.  Only under capture by default (an eager batch-1 forward is bound by the host's launch rate: 307 -> 263 fps
@@ -78,21 +74,15 @@ _CONFIG = dict(
     # sides of every fork passes; the soak reproduced the mismatch on ONE stream; root cause: a packed-fp32 erratum, csrc/common.h).
     BRANCH_STREAMS_BWD=True,
     BRANCH_STREAMS_BWD_MIN_BATCH=8,
-    # which branch leaves the capturing stream: the longer chain (branch 1) forks (690 -> 737 fps at batch 1); False = branch 2
-    BRANCH_STREAMS_SWAP=True,
-    STEM_FOLD=True,             # padded / folded RGB stem input (the streaming stem kernels need it)
     JOINT_ENTRY=1,              # Inception blocks run their three input-side 1x1x1 convs as one (model_utils._Mixed._fwd_joint)
     BN_BWD_FUSE=1,              # the stem's BN-backward apply pass folded into its weight-gradient kernel
     SHARE_SKIP_GRAD=True,       # a decoder skip's gradient lives in the T-concat's gradient (no copy in backward)
-    # weight gradients of the BN-free (decoder) convs wait until the tape reaches the encoder (+0.5 % on the step at 192 clips)
+    # weight gradients of the BN-free (decoder) convs wait until the tape reaches the encoder (+0.5 % on the step at 192 clips).
+    # Never in fp32s: the weight-gradient stream is the longer one there (deferring: 212.5 -> 207.3 clips/s at 64 clips)
     DEFER_DECODER_WGRAD=1,
-    DEFER_DECODER_WGRAD_F32S=0,  # fp32s: the weight-gradient stream is the longer one there (207.3 -> 212.5 clips/s at 64 clips)
-    PERSISTENT_DW=1,            # packed weight-gradient workspaces owned by the conv plans, re-zeroed by the unpack kernel
     # consumer-side BN costs the MFMA kernels 20-27 %; writing relu(bn(x)) out once costs two passes over x: materialise the
     # input of a conv when N * taps is at least this (0 = never; whole step: never 478 clips/s, 400: 483, 800: 539, 2500: 485)
     MATERIALIZE_NT=800,
-    SPLIT_WGRAD_BF16=1,         # fp32s weight gradient as three launches of the bf16 kernels over hi / lo planes
-    SPLIT_IN_APPLY=1,           # fp32s: the planes of dy leave with the BatchNorm-backward apply pass that produces dy
     # a data gradient that is the LAST writer of the gradient behind BatchNorm + ReLU layers also writes their backward partial
     # sums (VinetConvDesc::bnb_*): no reduce pass over (dz, z) for those layers.  0 = off, 1 = the stem's fused temporal data
     # gradient only (round 4), 2 = every data gradient the library can do it for (round 5: the shared conv epilogue, conv_bnb.hip).
@@ -543,7 +533,6 @@ class Ctx:
         self.tape = [] if record else None
         self.stream = _stream_for(device)
         self._bnb = {}           # id(storage owner) -> [(c0, c1, partials, rows, root, marks)]: BN-backward partial sums that data gradients left
-        self._side_rr = -1       # weight-gradient stream the last job went to (jobs are dealt round robin)
         # optional entry points of this library object, asked once per pass (maxpool_forward, _pool_bwd_defers)
         lib = self.lib
         self.lib_keeps = getattr(lib, "vinet_maxpool3d_keep_ok", None) is not None and hasattr(lib, "vinet_maxpool3d_keep")
@@ -554,12 +543,12 @@ class Ctx:
     def _begin_backward(self, capturing=False):
         """the state of one backward pass (run_backward; a fresh Ctx is ready for a standalone conv backward, ops.py)"""
         self.capturing = capturing      # the pass runs inside a stream capture
-        self.side_used = False   # a weight-gradient stream got work: the pass ends with the main stream waiting for them
+        self.side_used = False   # the weight-gradient stream got work: the pass ends with the main stream waiting for it
         self._side_keep = []
         self._deferred = []      # weight-gradient jobs waiting for their (shared) join: _schedule_wgrad / flush_deferred
         self._unpack_jobs = []
         self._dw_plans = []
-        self._joined = False     # flush_deferred has joined every weight-gradient stream: its jobs skip their own join
+        self._joined = False     # flush_deferred has joined the weight-gradient stream: its jobs skip their own join
         self.bwd_cm = None       # on_stream() of the branch stream the pass is on (markers of model_utils._Mixed._fwd_joint_forked_train)
         self._tape_left = len(self.tape) if self.tape else 0        # nodes still to run, the current one included
 
@@ -574,7 +563,7 @@ class Ctx:
         if LAUNCH_LOG is not None:
             LAUNCH_LOG.append((name, args[-1] if args else None, tag))
         if _ABLATE and (name in _ABLATE or (tag is not None and any(a in tag for a in _ABLATE_TAGS))):
-            return          # tuning only (VINET_ABLATE): the launch is skipped, results are garbage, the step time is the point
+            return          # tuning only (option ABLATE): the launch is skipped, results are garbage, the step time is the point
         prof = PROFILER
         if prof is not None and self.device.type == "cuda" and prof.want(tag or name):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -591,11 +580,11 @@ class Ctx:
         if self.tape is not None:
             self.tape.append(fn)
 
-    def side_stream(self, k=0):
-        """k-th weight-gradient stream of this device (None on the CPU test double)"""
+    def side_stream(self):
+        """the weight-gradient stream of this device (None on the CPU test double)"""
         if not WGRAD_SIDE_STREAM or self.device.type != "cuda":
             return None
-        return self._stream(k)
+        return self._stream(0)
 
     def _stream(self, k):
         st = _SIDE_STREAMS.get((self.device.index, k))
@@ -624,12 +613,6 @@ class Ctx:
         weight-gradient stream).  fork=False: not a branch fork (DBG_SPIN_FORK); weight-gradient streams have DBG_SPIN_SIDE"""
         return _OnStream(self, st, fork)
 
-    def side_streams(self):
-        """every weight-gradient stream in use (N_SIDE_STREAMS of them; empty without a GPU)"""
-        if self.side_stream() is None:
-            return []
-        return [self.side_stream(k) for k in range(N_SIDE_STREAMS)]
-
     def keep(self, *tensors):
         """hold tensors that a side-stream kernel reads or writes until run_backward has joined the streams: the caching
         allocator would otherwise hand a block released by the main stream's Python frame to the next main-stream
@@ -650,10 +633,7 @@ class Ctx:
             return
         side = self.side_stream()
         if side is not None:
-            # (every weight-gradient stream the jobs are dealt over: a job on stream k >= 1 skips its own join when _joined is set)
-            cur = torch.cuda.current_stream(self.device)
-            for st in self.side_streams():
-                st.wait_stream(cur)
+            side.wait_stream(torch.cuda.current_stream(self.device))
             self._joined = True
         try:
             for job in jobs:
@@ -687,12 +667,11 @@ class Ctx:
     def finish_backward(self):
         """the tail of a backward pass (run_backward; one conv's standalone backward, ops.py): the weight-gradient jobs still
         waiting, the unpack launch behind them, and the main stream (the optimizer, every buffer release that follows) behind
-        the weight-gradient streams if they got work"""
+        the weight-gradient stream if it got work"""
         self.flush_deferred()
         self.flush_unpack()
         if self.side_used:
-            for st in self.side_streams():
-                torch.cuda.current_stream(self.device).wait_stream(st)
+            torch.cuda.current_stream(self.device).wait_stream(self.side_stream())
 
     def run_backward(self):
         self._begin_backward(self.device.type == "cuda" and torch.cuda.is_current_stream_capturing())
@@ -711,8 +690,9 @@ class Ctx:
             # and a failed capture is discarded as a whole anyway.)
             if self.device.type == "cuda" and not self.capturing:
                 try:
-                    for st in self.side_streams():
-                        torch.cuda.current_stream(self.device).wait_stream(st)
+                    side = self.side_stream()
+                    if side is not None:
+                        torch.cuda.current_stream(self.device).wait_stream(side)
                     torch.cuda.current_stream(self.device).synchronize()
                 except Exception:
                     pass
@@ -1581,7 +1561,7 @@ def _bn_backward_apply(ctx, plan, x, res, keep, dz, pool, c1, c2):
         _set_bnb(q, *fused)
         if ctx.lib.vinet_conv3d_wgrad_fuses_bn_bwd(C.byref(q)):
             return dz, fused, None
-    if (SPLIT_IN_APPLY and SPLIT_WGRAD_BF16 and ctx.cdt == F32S and plan.wants_wgrad() and dz.dt == F32 and
+    if (ctx.cdt == F32S and plan.wants_wgrad() and dz.dt == F32 and
             out.dt == F32 and dz.C % 8 == 0 and dz.ld % 8 == 0 and out.ld % 8 == 0 and ctx.device.type == "cuda"):
         # fp32s: the hi / lo planes of dy (an operand of the three bf16 weight-gradient launches) leave with the apply pass
         dh = View.alloc(dz.B, dz.T, dz.H, dz.W, dz.C, BF16, dz.device)
@@ -1636,14 +1616,13 @@ class _WgradJob:
         self.fused_bnb, self.dy_planes = fused_bnb, dy_planes       # what stage 1 left: _bn_backward_apply
         # fp32s: hi / lo planes of both operands for the three bf16 launches -- any conv with whole 8-channel groups, and the
         # folded RGB stem (the row-streaming strip kernel, wgrad_hs.hip, over planes of the padded clip)
-        self.want_planes = bool(SPLIT_WGRAD_BF16 and ctx.cdt == F32S and fused_bnb is None and dy.C % 8 == 0 and x.v.dt == F32 and dy.dt == F32 and
+        self.want_planes = bool(ctx.cdt == F32S and fused_bnb is None and dy.C % 8 == 0 and x.v.dt == F32 and dy.dt == F32 and
                                 ((not plan.stem and x.fold is None and x.v.C % 8 == 0) or
                                  (plan.stem and x.fold is not None and x.scale is None and x.v.off == 0)))
 
     def __call__(self):
         ctx = self.ctx
-        ctx._side_rr = (ctx._side_rr + 1) % N_SIDE_STREAMS
-        side = ctx.side_stream(ctx._side_rr)
+        side = ctx.side_stream()
         if side is not None:
             if not ctx._joined:
                 side.wait_stream(torch.cuda.current_stream(ctx.device))   # dy (and everything before it) is ready
@@ -1660,11 +1639,9 @@ class _WgradJob:
         # persistent workspace, handed back zeroed by the unpack kernel
         # (a channel-padded head -- rows past plan.N are never unpacked, so whatever accumulates there over the steps is
         #  never read -- keeps a persistent workspace too: no allocation and no fill on the weight-gradient stream)
-        persistent = bool(PERSISTENT_DW)
-        dw = plan.dw_workspace(ctx, nsl * Ny * kp) if persistent else ctx.f32(nsl * Ny * kp, zero=True)
-        if persistent:
-            ctx._dw_plans.append(plan)
-        if persistent and any(j[0] == dw.data_ptr() for j in ctx._unpack_jobs):
+        dw = plan.dw_workspace(ctx, nsl * Ny * kp)
+        ctx._dw_plans.append(plan)
+        if any(j[0] == dw.data_ptr() for j in ctx._unpack_jobs):
             # this plan already ran in this backward (a module used twice in one forward): its workspace holds the
             # first use's gradient, and the kernels may STORE their result (no split-K, no atomics: "dw is zero on
             # entry").  Hand that gradient over and get the workspace back zeroed first.
@@ -1675,8 +1652,8 @@ class _WgradJob:
         # the LAST node of the tape (the RGB stem: its input needs no gradient, so nothing of the main stream is
         # left beside its weight gradient) may take the whole chip; any other conv without a data gradient (the first
         # SoundNet layer) still has main-stream work beside it and keeps the cap
-        tail = TAIL_WGRAD_FULL and side is not None and not x.needs_grad and ctx._tape_left <= 1
-        wd.max_cus = 256 if (tail or side is None) else (WGRAD_CUS_DEC if self.bn_free else WGRAD_CUS)
+        tail = side is not None and not x.needs_grad and ctx._tape_left <= 1
+        wd.max_cus = 256 if (tail or side is None) else WGRAD_CUS
         if DBG_SPIN_SIDE and side is not None:
             ctx.lib.vinet_debug_spin(DBG_SPIN_SIDE, ctx.stream)
         if self.want_planes:
@@ -1697,10 +1674,10 @@ class _WgradJob:
             ctx.call("vinet_conv3d_wgrad", C.byref(wd), ctx.stream, tag=tag, work=work)
         if Ny != plan.N:
             assert plan.ntaps == 1, "channel-padded outputs are only supported for 1x1x1 convs"
-        if persistent and MULTI_UNPACK and PARAM_GRAD_HOOK is None and N_SIDE_STREAMS == 1:
+        if MULTI_UNPACK and PARAM_GRAD_HOOK is None:
             ctx._unpack_jobs.extend(plan.unpack_jobs(dw))      # one launch for all of them at the end of backward
         else:
-            plan.unpack_wgrad(ctx, dw, clear=persistent)
+            plan.unpack_wgrad(ctx, dw, clear=True)
         if side is not None:
             ctx.keep(dw, dy.buf, x.v.buf, x.scale, x.shift, *(fused_bnb[2:] if fused_bnb is not None else ()))
 
@@ -1714,8 +1691,8 @@ def _schedule_wgrad(ctx, job):
     # (Under stream capture too: the wrong encoder gradients of round 3's captured step came from the per-job joins of the
     # flush -- a fan-out of redundant graph edges that ROCm 7.2 replays wrongly, see Ctx.flush_deferred -- not from the
     # deferral; with one join per batch the captured step follows the eager trajectory.)
-    defer = DEFER_DECODER_WGRAD_F32S if ctx.cdt == F32S else DEFER_DECODER_WGRAD
-    group = WGRAD_GROUP_CAPTURE if ctx.capturing else WGRAD_GROUP
+    defer = DEFER_DECODER_WGRAD and ctx.cdt != F32S
+    group = WGRAD_GROUP_CAPTURE if ctx.capturing else 1
     if defer and job.bn_free and ctx.side_stream() is not None:
         ctx._deferred.append(job)
     elif group > 1 and ctx.side_stream() is not None:

@@ -205,14 +205,10 @@ class _Mixed(_Block):
                     m.bn.note_training_step()
                 self.__dict__["_vinet_joint_fold"].clear()
             fork[0].wait_stream(main)
-            if E.BRANCH_STREAMS_SWAP:
-                with ctx.on_stream(fork[0]):
-                    self.branch1[1]._fwd(ctx, r1, cat.sub_chan(o1, o2))
-                self.branch2[1]._fwd(ctx, r2, cat.sub_chan(o2, o3))
-            else:
-                with ctx.on_stream(fork[0]):
-                    self.branch2[1]._fwd(ctx, r2, cat.sub_chan(o2, o3))
+            # the longer chain (branch 1) leaves the capturing stream, branch 2 stays: 690 -> 737 fps at batch 1 against the reverse
+            with ctx.on_stream(fork[0]):
                 self.branch1[1]._fwd(ctx, r1, cat.sub_chan(o1, o2))
+            self.branch2[1]._fwd(ctx, r2, cat.sub_chan(o2, o3))
             main.wait_stream(fork[0])
             main.wait_stream(fork[1])
             return cat

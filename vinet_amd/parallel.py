@@ -245,7 +245,8 @@ class GradientBuckets:
             if comm is None:
                 comm = self._comm_streams[dev.index] = torch.cuda.Stream(dev)
             comm.wait_stream(torch.cuda.current_stream(dev))              # BatchNorm / bias gradients and everything before them
-            for side in (ctx.side_streams() if ctx is not None else []):
+            side = ctx.side_stream() if ctx is not None else None
+            if side is not None:
                 comm.wait_stream(side)                                    # the weight-gradient kernels launched so far
             with torch.cuda.stream(comm):
                 if self._t0 is not None:
