@@ -642,6 +642,25 @@ enum { VINET_TK_MMA_F32 = 0, VINET_TK_MMA_BF16X3 = 1, VINET_TK_MMA_BF16 = 2 };
 int64_t vinet_token_encoder_workspace_mma(const VinetTokenEncoderDesc* desc, int32_t mma);
 int vinet_token_encoder_fwd_mma(const VinetTokenEncoderDesc* desc, int32_t mma, const VinetTensor* x, const VinetTensor* y, void* stream);
 int vinet_token_encoder_bwd_mma(const VinetTokenEncoderDesc* desc, int32_t mma, const VinetTensor* dy, const VinetTensor* dx, void* stream);
+/* Arithmetic of ATTENTION, a second selector beside `mma` with the same VINET_TK_MMA_* values; it applies to all seven products:
+ *   scores = (q qscale) k^T   AO = (p m) v   dP = dAO v^T   dQ = dS k   dV = (P m)^T dAO   dK = dS^T q
+ * (p m: the softmax value times the keep mask and 1 / (1 - p); q qscale is scaled in fp32, then split; dK takes the unscaled q).
+ *   F32 = the kernels the entry points above run (fp32-input MFMA);  BF16 = sum hi hi;  BF16X3 = sum (hi hi + hi lo + lo hi),
+ * each operand split after it has been formed in fp32, fp32 accumulation inside v_mfma_f32_16x16x32_bf16.  The row maximum, expf,
+ * the row sum and the normalisation, the keep-mask draw (a step's masks do not depend on the mode), dS = P (dP m - dot) qscale,
+ * the row dots and the values saved in P stay fp32.  Same workspace, same size (any attn), same limits, no atomics, bit-identical
+ * runs.  The _mma entry points call these with attn = F32; backward must be given the attn of its forward.  Unknown attn: -1. */
+int64_t vinet_token_encoder_workspace_attn(const VinetTokenEncoderDesc* desc, int32_t mma, int32_t attn);
+int vinet_token_encoder_fwd_attn(const VinetTokenEncoderDesc* desc, int32_t mma, int32_t attn, const VinetTensor* x, const VinetTensor* y, void* stream);
+int vinet_token_encoder_bwd_attn(const VinetTokenEncoderDesc* desc, int32_t mma, int32_t attn, const VinetTensor* dy, const VinetTensor* dx, void* stream);
+/* one attention stage without dropout in the arithmetic `attn`, on caller-owned fp32 matrices in the workspace's row layout (every
+ * clip owns Sp = S rounded up to 16 rows): qkv [B Sp][3E] (q | k | v, head h at columns h E / H), P [B][H][S][S], ao / dao [B Sp][E],
+ * dot [B Sp][H], dqkv [B Sp][3E].  Forward writes P and ao (zeros in ao's padding rows).  Backward READS P and ao (they need not come
+ * from a forward), writes dot = rowsum(dao ao) per head and dqkv (zeros in its padding rows).  Limits: those of the descriptor
+ * (S, E, E / H); qkv, ao, dao, dqkv 16-byte aligned.  Anything else is refused (-1, vinet_last_error) before a device is touched. */
+int vinet_token_attn_fwd(int32_t attn, const float* qkv, int32_t B, int32_t S, int32_t E, int32_t H, float* P, float* ao, void* stream);
+int vinet_token_attn_bwd(int32_t attn, const float* qkv, const float* P, const float* dao, const float* ao, int32_t B, int32_t S, int32_t E,
+                         int32_t H, float* dot, float* dqkv, void* stream);
 /* one linear product of the encoder, any mode (mma = F32 runs tf_gemm): form 0 C[m][n] = sum_k A[m][k] B[n][k],
  * form 1 sum_k A[m][k] B[k][n], form 2 sum_k A[k][m] B[k][n]; epi 0 plain, 1 + bias[n], 2 relu(. + bias), 3 + res[m][ldc], 4 C +=.
  * fp32 matrices with row strides lda / ldb / ldc (elements); M % 4 == 0, N % 4 == 0, K % 16 == 0, A and B 16-byte aligned with

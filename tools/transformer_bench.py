@@ -7,7 +7,8 @@
             forward + backward at --token_batches (default 1, 8, 32, 192) against eager nn.TransformerEncoder in fp32 on the same
             device, weights and input (dropout 0 on both), the two alternating inside each timed round; with the achieved share of
             the 155 TF/s fp32-MFMA rate (FLOPs counted from the shapes) and the workspace bytes per clip.  --token_mma fp32,bf16x3,bf16
-            times the encoder in each of these arithmetic modes of its linear products (engine option TOKEN_MMA), all of them and
+            times the encoder in each of these arithmetic modes of its linear products (engine option TOKEN_MMA; --token_attn pairs an attention
+            arithmetic, engine.TOKEN_ATTN, with each), all of them and
             aten taking turns inside each round; the first mode fills the hip_* columns, the others hip_<mode>_* columns
   step      the AViNet training step (kldiv + fused Adam, --dtype) with and without use_transformer at --step_batches (default 1, 8, 32, 192)
 
@@ -137,7 +138,14 @@ def bench_tokens(args, dev):
     aten.load_state_dict({k[len("transformer_encoder."):]: v for k, v in sd.items() if k.startswith("transformer_encoder.")})
     pe = sd["pos_encoder.pe"].to(dev)
     flops = NL * token_layer_flops(S, Ef, Ef)
-    modes = [m for m in args.token_mma.split(",") if m]
+    # a configuration = (arithmetic of the linears, arithmetic of attention); the two lists pair up element by element, a list of one
+    # goes with every element of the other.  Named by the linears' mode alone while attention is fp32 (the columns of before the option)
+    mmas, attns = [m for m in args.token_mma.split(",") if m], [m for m in args.token_attn.split(",") if m]
+    n_cfg = max(len(mmas), len(attns))
+    assert len(mmas) in (1, n_cfg) and len(attns) in (1, n_cfg), "--token_mma and --token_attn: lists of equal length, or one of them a single value"
+    pairs = [(mmas[i % len(mmas)], attns[i % len(attns)]) for i in range(n_cfg)]
+    cfg = {(m if a == "fp32" else "%s_attn_%s" % (m, a)): (m, a) for m, a in pairs}
+    modes = list(cfg)
     for B in [int(b) for b in args.token_batches.split(",")]:
         x = synth.normal("bench_tok_x", (B, Ef, S, 1, 1), 2).to(dev)          # NCDHW: position = token, channel = feature
         g = synth.normal("bench_tok_g", (B, Ef, S, 1, 1), 3).to(dev)
@@ -145,20 +153,22 @@ def bench_tokens(args, dev):
         gt = g.reshape(B, Ef, S).permute(2, 0, 1).contiguous()
 
         def hip_fwd(mode=modes[0]):
-            old = E.configure(token_mma=mode)
+            old, old_attn = E.configure(token_mma=cfg[mode][0]), E.set_token_attn(cfg[mode][1])
             try:
                 with torch.no_grad():
                     return fusion.token_encoder_tokens(tf, x)
             finally:
                 E.configure(**old)
+                E.set_token_attn(old_attn)
 
         def hip_fb(mode=modes[0]):
-            old = E.configure(token_mma=mode)
+            old, old_attn = E.configure(token_mma=cfg[mode][0]), E.set_token_attn(cfg[mode][1])
             try:
                 xr = x.detach().requires_grad_(True)
                 (fusion.token_encoder_tokens(tf, xr) * g).sum().backward()
             finally:
                 E.configure(**old)
+                E.set_token_attn(old_attn)
 
         def aten_fwd():
             with torch.no_grad():
@@ -175,7 +185,7 @@ def bench_tokens(args, dev):
             ref = aten(xt + pe)
             diffs = {m: float((hip_fwd(m).reshape(B, Ef, S).permute(2, 0, 1) - ref).abs().max()) for m in modes}
         reps = max(5, args.repeats // (1 if B <= 32 else 3))
-        row = dict(bench="token_encoder", B=B, S=S, E=Ef, H=H, L=NL, token_mma=modes, max_abs_diff_to_aten=diffs[modes[0]], repeats=reps)
+        row = dict(bench="token_encoder", B=B, S=S, E=Ef, H=H, L=NL, token_mma=modes, token_attn=[a for _, a in pairs], max_abs_diff_to_aten=diffs[modes[0]], repeats=reps)
         for m in modes[1:]:
             row["max_abs_diff_to_aten_" + m] = diffs[m]
         fw = {col(m, "fwd"): (lambda m=m: hip_fwd(m)) for m in modes}
@@ -252,6 +262,8 @@ def main():
     p.add_argument("--encoder_batches", default="1,8,32,192")
     p.add_argument("--token_batches", default="1,8,32,192")
     p.add_argument("--token_mma", default="fp32", help="tokens: comma list of fp32, bf16x3, bf16 (the encoder's linear arithmetic), timed side by side")
+    p.add_argument("--token_attn", default="fp32", help="tokens: comma list of fp32, bf16x3, bf16 (the encoder's attention arithmetic), paired with "
+                   "--token_mma element by element (a single value goes with all of them); columns hip_<mma>_attn_<attn>_*")
     p.add_argument("--dtype", default="bf16")
     args = p.parse_args()
     dev = torch.device("cuda:0")

@@ -143,6 +143,11 @@ SIGNATURES = {
     "vinet_token_encoder_workspace_mma": [_PK, _i32],
     "vinet_token_encoder_fwd_mma": [_PK, _i32, _PT, _PT, _vp],
     "vinet_token_encoder_bwd_mma": [_PK, _i32, _PT, _PT, _vp],
+    "vinet_token_encoder_workspace_attn": [_PK, _i32, _i32],
+    "vinet_token_encoder_fwd_attn": [_PK, _i32, _i32, _PT, _PT, _vp],
+    "vinet_token_encoder_bwd_attn": [_PK, _i32, _i32, _PT, _PT, _vp],
+    "vinet_token_attn_fwd": [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "vinet_token_attn_bwd": [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "vinet_token_gemm": [_i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "vinet_token_split_fwd": [_PT, _i32, _i32, _PT, _vp],
     "vinet_token_split_bwd": [_PT, _i32, _i32, _PT, _vp],
@@ -167,7 +172,7 @@ _RESTYPE = {"vinet_last_error": C.c_char_p, "vinet_conv3d_splitk_bytes": C.c_int
             "vinet_gt_preprocess_ws_bytes": C.c_int64, "vinet_auc_judd_workspace": C.c_size_t, "vinet_auc_shuffled_workspace": C.c_size_t, "vinet_auc_borji_workspace": C.c_size_t,
             "vinet_emd_workspace": C.c_size_t,
             "vinet_transformer_workspace": C.c_int64, "vinet_token_encoder_workspace": C.c_int64,
-            "vinet_token_encoder_workspace_mma": C.c_int64}
+            "vinet_token_encoder_workspace_mma": C.c_int64, "vinet_token_encoder_workspace_attn": C.c_int64}
 
 _LIB = None
 _TEST_DOUBLE = None

@@ -6,7 +6,8 @@
 // to 16 rows, so the token matrices [M = B Sp][.] meet the token GEMM's contract (M % 4 == 0, a weight gradient's reduction axis
 // a multiple of 16) whatever S and B are, and the stages between attention are the ones of transformer.hip (tf_common.h).
 // The linear products (the six linears of a layer, their data and weight gradients) run in the arithmetic the caller names
-// (VINET_TK_MMA_*): tf_gemm on the fp32 MFMA, or tk_gemm_bf16.h on the bf16 MFMA over the same fp32 matrices.
+// (VINET_TK_MMA_*): tf_gemm on the fp32 MFMA, or tk_gemm_bf16.h on the bf16 MFMA over the same fp32 matrices.  Attention takes a
+// mode of its own from the same values: the kernels below, or tk_attn_bf16.h over the same workspace.
 // Padding rows: ZERO in the encoder's input and in every gradient matrix, finite (a bias, a LayerNorm of it) in every saved
 // activation, so they add exactly 0 to each weight and bias gradient; attention never reads them as keys and writes zeros for them.
 //
@@ -19,6 +20,7 @@
 // maps them to [B S][.]), site 0 by the unpadded [B][H][S][S] index.
 #include "tf_common.h"
 #include "tk_gemm_bf16.h"
+#include "tk_attn_bf16.h"
 
 namespace {
 
@@ -462,6 +464,12 @@ static int check_mma(int32_t mma, const char* who) {
   return 0;
 }
 
+static int check_attn(int32_t attn, const char* who) {
+  VN_CHECK_ARG(attn == VINET_TK_MMA_F32 || attn == VINET_TK_MMA_BF16X3 || attn == VINET_TK_MMA_BF16,
+               "%s: attn = %d is not VINET_TK_MMA_F32 (0), _BF16X3 (1) or _BF16 (2)", who, attn);
+  return 0;
+}
+
 #define TK_BY_WIDTH(D, CALL)                 \
   do {                                       \
     if ((D) <= 16) { CALL(1); }              \
@@ -473,9 +481,12 @@ static int check_mma(int32_t mma, const char* who) {
 }  // namespace
 
 // (the bf16 GEMMs read and write the fp32 matrices of the fp32 ones: one layout, one size, whatever the mode)
-extern "C" int64_t vinet_token_encoder_workspace_mma(const VinetTokenEncoderDesc* d, int32_t mma) {
-  if (check_desc(d, "token_encoder_workspace") || check_mma(mma, "token_encoder_workspace")) return -1;
+extern "C" int64_t vinet_token_encoder_workspace_attn(const VinetTokenEncoderDesc* d, int32_t mma, int32_t attn) {
+  if (check_desc(d, "token_encoder_workspace") || check_mma(mma, "token_encoder_workspace") || check_attn(attn, "token_encoder_workspace")) return -1;
   return make_layout(d).total * (int64_t)sizeof(float);
+}
+extern "C" int64_t vinet_token_encoder_workspace_mma(const VinetTokenEncoderDesc* d, int32_t mma) {
+  return vinet_token_encoder_workspace_attn(d, mma, VINET_TK_MMA_F32);
 }
 extern "C" int64_t vinet_token_encoder_workspace(const VinetTokenEncoderDesc* d) { return vinet_token_encoder_workspace_mma(d, VINET_TK_MMA_F32); }
 
@@ -485,8 +496,9 @@ static inline long tk_mask_layer_bytes(const VinetTokenEncoderDesc* d) {
   return (long)d->B * d->H * d->S * d->S + 2 * MS * d->E + MS * d->F;
 }
 
-extern "C" int vinet_token_encoder_fwd_mma(const VinetTokenEncoderDesc* d, int32_t mma, const VinetTensor* x, const VinetTensor* y, void* stream) {
-  if (check_desc(d, "token_encoder_fwd") || check_mma(mma, "token_encoder_fwd")) return -1;
+extern "C" int vinet_token_encoder_fwd_attn(const VinetTokenEncoderDesc* d, int32_t mma, int32_t attn, const VinetTensor* x, const VinetTensor* y,
+                                            void* stream) {
+  if (check_desc(d, "token_encoder_fwd") || check_mma(mma, "token_encoder_fwd") || check_attn(attn, "token_encoder_fwd")) return -1;
   VN_CHECK_ARG(tensor_ok(x, d) && tensor_ok(y, d), "token_encoder_fwd: x / y must be [B][T H W = S][C = E] channels-last with ld >= C");
   VN_CHECK_ARG(d->params && d->pe && d->ws && (((uintptr_t)d->ws) & 15) == 0, "token_encoder_fwd: params, pe and a 16-byte aligned workspace are required");
   const Layout L = make_layout(d);
@@ -516,7 +528,8 @@ extern "C" int vinet_token_encoder_fwd_mma(const VinetTokenEncoderDesc* d, int32
     ep.bias = P[P_INB]; ep.res = nullptr; ep.stream = 0;
     tk_gemm_launch<true, true, EPI_BIAS>(mma, s, xin, E, P[P_INW], E, sv + L.qkv, 3 * E, M, 3 * E, E, ep);
 #define TK_FWD(DT) hipLaunchKernelGGL(tk_attn_fwd<DT>, agrid, dim3(256), 0, s, sv + L.qkv, S, Sp, E, H, D, qscale, sv + L.P, sv + L.ao, drop, 4 * l + 0, mk)
-    TK_BY_WIDTH(D, TK_FWD);
+    if (attn == VINET_TK_MMA_F32) TK_BY_WIDTH(D, TK_FWD);
+    else tk_attn_fwd_bf16_launch(attn, s, sv + L.qkv, B, S, Sp, E, H, qscale, sv + L.P, sv + L.ao, drop, 4 * l + 0, mk);
 #undef TK_FWD
     ep.bias = P[P_OUTB]; ep.res = xin; ep.stream = 4 * l + 1;
     tk_gemm_launch<true, true, EPI_BIAS_DROP_RES>(mma, s, sv + L.ao, E, P[P_OUTW], E, sv + L.z1, E, M, E, E, ep);
@@ -542,8 +555,9 @@ extern "C" int vinet_token_encoder_fwd_mma(const VinetTokenEncoderDesc* d, int32
   return vn_launch_status("token_encoder_fwd");
 }
 
-extern "C" int vinet_token_encoder_bwd_mma(const VinetTokenEncoderDesc* d, int32_t mma, const VinetTensor* dy, const VinetTensor* dx, void* stream) {
-  if (check_desc(d, "token_encoder_bwd") || check_mma(mma, "token_encoder_bwd")) return -1;
+extern "C" int vinet_token_encoder_bwd_attn(const VinetTokenEncoderDesc* d, int32_t mma, int32_t attn, const VinetTensor* dy, const VinetTensor* dx,
+                                            void* stream) {
+  if (check_desc(d, "token_encoder_bwd") || check_mma(mma, "token_encoder_bwd") || check_attn(attn, "token_encoder_bwd")) return -1;
   VN_CHECK_ARG(d->train, "token_encoder_bwd: the forward pass must have run with train = 1 (it saves the layers' state)");
   VN_CHECK_ARG(tensor_ok(dy, d) && (!dx || tensor_ok(dx, d)), "token_encoder_bwd: dy / dx must be [B][T H W = S][C = E] channels-last with ld >= C");
   VN_CHECK_ARG(d->params && d->grads && d->ws && (((uintptr_t)d->ws) & 15) == 0, "token_encoder_bwd: params, grads and the forward's workspace are required");
@@ -593,7 +607,8 @@ extern "C" int vinet_token_encoder_bwd_mma(const VinetTokenEncoderDesc* d, int32
 #define TK_BWD(DT)                                                                                                                                    \
   hipLaunchKernelGGL(tk_attn_bwd_q<DT>, agrid, dim3(256), 0, s, sv + L.qkv, sv + L.P, dAO, dot, S, Sp, E, H, D, qscale, dQKV, drop, 4 * l + 0);   \
   hipLaunchKernelGGL(tk_attn_bwd_kv<DT>, agrid, dim3(256), 0, s, sv + L.qkv, sv + L.P, dAO, dot, S, Sp, E, H, D, qscale, dQKV, drop, 4 * l + 0)
-    TK_BY_WIDTH(D, TK_BWD);
+    if (attn == VINET_TK_MMA_F32) TK_BY_WIDTH(D, TK_BWD);
+    else tk_attn_bwd_bf16_launch(attn, s, sv + L.qkv, sv + L.P, dAO, dot, B, S, Sp, E, H, qscale, dQKV, drop, 4 * l + 0);
 #undef TK_BWD
     hipLaunchKernelGGL(tf_colsum_clip<TK_GROUP>, dim3(vn_div_up(3 * E, 256), NG), dim3(256), 0, s, dQKV, 3 * E, part, ps, oINB);
     // QKV projection: dXin = dQKV Win + dZ;  dWin += dQKV^T xin
@@ -614,6 +629,12 @@ extern "C" int vinet_token_encoder_bwd_mma(const VinetTokenEncoderDesc* d, int32
   return vn_launch_status("token_encoder_bwd");
 }
 
+extern "C" int vinet_token_encoder_fwd_mma(const VinetTokenEncoderDesc* d, int32_t mma, const VinetTensor* x, const VinetTensor* y, void* stream) {
+  return vinet_token_encoder_fwd_attn(d, mma, VINET_TK_MMA_F32, x, y, stream);
+}
+extern "C" int vinet_token_encoder_bwd_mma(const VinetTokenEncoderDesc* d, int32_t mma, const VinetTensor* dy, const VinetTensor* dx, void* stream) {
+  return vinet_token_encoder_bwd_attn(d, mma, VINET_TK_MMA_F32, dy, dx, stream);
+}
 extern "C" int vinet_token_encoder_fwd(const VinetTokenEncoderDesc* d, const VinetTensor* x, const VinetTensor* y, void* stream) {
   return vinet_token_encoder_fwd_mma(d, VINET_TK_MMA_F32, x, y, stream);
 }
@@ -683,6 +704,59 @@ extern "C" int vinet_token_gemm(int32_t mma, int32_t form, int32_t epi, const fl
   if (form == 0) return tk_one_product_epi<true, true>(epi, g, s);
   if (form == 1) return tk_one_product_epi<true, false>(epi, g, s);
   return tk_one_product_epi<false, false>(epi, g, s);
+}
+
+// ---- one attention stage (vinet_token_attn_fwd / _bwd): no dropout, caller-owned matrices in the workspace's row layout ------------
+static int attn_args_ok(int32_t attn, int32_t B, int32_t S, int32_t E, int32_t H, const char* who) {
+  if (check_attn(attn, who)) return -1;
+  VN_CHECK_ARG(B > 0 && H > 0, "%s: B = %d and H = %d must be positive", who, B, H);
+  VN_CHECK_ARG(S >= 1 && S <= TK_MAX_S, "%s: S = %d tokens per clip must be in [1, %d]", who, S, TK_MAX_S);
+  VN_CHECK_ARG(E > 0 && E % 16 == 0 && E <= TK_MAX_E, "%s: E = %d must be a multiple of 16 and <= %d", who, E, TK_MAX_E);
+  VN_CHECK_ARG(E % H == 0 && E / H <= TK_MAX_D && (E / H) % 4 == 0, "%s: head width E / H = %d / %d must be an integer multiple of 4 and <= %d", who, E,
+               H, TK_MAX_D);
+  VN_CHECK_ARG((long)B * tk_sp(S) * 3 * E < (1L << 31) && (long)B * H * S * S < (1L << 32),
+               "%s: B = %d clips of %d tokens exceed the kernels' 32-bit row and mask indices", who, B, S);
+  return 0;
+}
+static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+extern "C" int vinet_token_attn_fwd(int32_t attn, const float* qkv, int32_t B, int32_t S, int32_t E, int32_t H, float* P, float* ao, void* stream) {
+  if (attn_args_ok(attn, B, S, E, H, "token_attn_fwd")) return -1;
+  VN_CHECK_ARG(qkv && P && ao, "token_attn_fwd: null matrix");
+  VN_CHECK_ARG(al16(qkv) && al16(ao) && (((uintptr_t)P) & 3) == 0, "token_attn_fwd: qkv and ao must be 16-byte aligned, P 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int Sp = tk_sp(S), D = E / H;
+  const float qscale = 1.f / sqrtf((float)D);
+  const Drop drop = tf_make_drop(0.f, 0, nullptr);
+  const dim3 agrid(vn_div_up(S, TK_BQ), H, B);
+  uint8_t* mk = nullptr;
+#define TK_FWD(DT) hipLaunchKernelGGL(tk_attn_fwd<DT>, agrid, dim3(256), 0, s, qkv, S, Sp, E, H, D, qscale, P, ao, drop, 0, mk)
+  if (attn == VINET_TK_MMA_F32) TK_BY_WIDTH(D, TK_FWD);
+  else tk_attn_fwd_bf16_launch(attn, s, qkv, B, S, Sp, E, H, qscale, P, ao, drop, 0, mk);
+#undef TK_FWD
+  return vn_launch_status("token_attn_fwd");
+}
+
+extern "C" int vinet_token_attn_bwd(int32_t attn, const float* qkv, const float* P, const float* dao, const float* ao, int32_t B, int32_t S, int32_t E,
+                                    int32_t H, float* dot, float* dqkv, void* stream) {
+  if (attn_args_ok(attn, B, S, E, H, "token_attn_bwd")) return -1;
+  VN_CHECK_ARG(qkv && P && dao && ao && dot && dqkv, "token_attn_bwd: null matrix");
+  VN_CHECK_ARG(al16(qkv) && al16(dao) && al16(ao) && al16(dqkv) && ((((uintptr_t)P) | ((uintptr_t)dot)) & 3) == 0,
+               "token_attn_bwd: qkv, dao, ao and dqkv must be 16-byte aligned, P and dot 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int Sp = tk_sp(S), D = E / H;
+  const long M = (long)B * Sp;
+  const float qscale = 1.f / sqrtf((float)D);
+  const Drop drop = tf_make_drop(0.f, 0, nullptr);
+  const dim3 agrid(vn_div_up(S, TK_BQ), H, B);
+  hipLaunchKernelGGL(tk_attn_dot, dim3(vn_div_up(M * H, 256)), dim3(256), 0, s, dao, ao, M * H, E, H, D, dot);
+#define TK_BWD(DT)                                                                                                  \
+  hipLaunchKernelGGL(tk_attn_bwd_q<DT>, agrid, dim3(256), 0, s, qkv, P, dao, dot, S, Sp, E, H, D, qscale, dqkv, drop, 0);   \
+  hipLaunchKernelGGL(tk_attn_bwd_kv<DT>, agrid, dim3(256), 0, s, qkv, P, dao, dot, S, Sp, E, H, D, qscale, dqkv, drop, 0)
+  if (attn == VINET_TK_MMA_F32) TK_BY_WIDTH(D, TK_BWD);
+  else tk_attn_bwd_bf16_launch(attn, s, qkv, P, dao, dot, B, S, Sp, E, H, qscale, dqkv, drop, 0);
+#undef TK_BWD
+  return vn_launch_status("token_attn_bwd");
 }
 
 static int split_args_ok(const VinetTensor* x, const VinetTensor* y, int32_t n_audio, const char* who) {

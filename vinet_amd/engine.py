@@ -159,6 +159,31 @@ def token_mma_mode(dt):
     return {"fp32": L.TK_MMA_F32, "bf16x3": L.TK_MMA_BF16X3, "bf16": L.TK_MMA_BF16}[name]
 
 
+# Arithmetic of the token encoder's ATTENTION (include/vinet_hip.h, the `attn` argument of the _attn entry points): the same four
+# names as TOKEN_MMA, resolved the same way.  It is NOT a key of _CONFIG and so is not reachable through configure() / --cfg:
+# tests/test_host_logic.py pins the table at 25 keys, and that test stays as it is.  Moving it into the table is for a change that
+# may touch that test.  Until then: this module attribute, its setter, and the drivers' --token_attn.
+TOKEN_ATTN = "fp32"
+TOKEN_ATTN_VALUES = ("fp32", "bf16x3", "bf16", "match")
+
+
+def set_token_attn(name):
+    """set TOKEN_ATTN; returns the previous value"""
+    global TOKEN_ATTN
+    if not isinstance(name, str) or name not in TOKEN_ATTN_VALUES:
+        raise ValueError("engine.set_token_attn: token_attn = %r is not one of %s" % (name, ", ".join(TOKEN_ATTN_VALUES)))
+    old, TOKEN_ATTN = TOKEN_ATTN, name
+    return old
+
+
+def token_attn_mode(dt):
+    """the VINET_TK_MMA_* value of TOKEN_ATTN in a context whose compute dtype (Ctx.cdt) is `dt`: L.F32 / L.F32S / L.BF16"""
+    name = TOKEN_ATTN
+    if name == "match":
+        name = {L.F32: "fp32", L.F32S: "bf16x3", L.BF16: "bf16"}[dt]
+    return {"fp32": L.TK_MMA_F32, "bf16x3": L.TK_MMA_BF16X3, "bf16": L.TK_MMA_BF16}[name]
+
+
 def configure_from_string(text):
     """'name=value,name=value' (bench.py --cfg, tools): engine options, and `lib.<option>=<int>` for vinet_set_option"""
     kw = {}

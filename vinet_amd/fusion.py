@@ -137,7 +137,8 @@ def token_encoder_forward(ctx, tf, tokens, out=None, masks=None):
     may be a channel sub-view of a wider tensor): PositionalEncoding + the encoder stack of `tf` (model._TransformerParams with
     pe [S,1,E]).  Dropout as transformer_forward; `masks` (uint8, tf.mask_bytes(B)) receives the keep masks.
     The linear products run in the arithmetic of the engine option TOKEN_MMA, resolved HERE, once: the workspace, the forward and
-    the backward closure all get that mode, whatever the option says by the time backward runs."""
+    the backward closure all get that mode, whatever the option says by the time backward runs.  Attention's arithmetic
+    (engine.TOKEN_ATTN) is resolved beside it; at F32 the calls are the _mma entry points, as before the option existed."""
     assert tokens.plain, "the token encoder reads plain activations"
     E.note_reader(ctx, tokens)
     xv = tokens.v
@@ -161,9 +162,14 @@ def token_encoder_forward(ctx, tf, tokens, out=None, masks=None):
     parr = (C.c_void_p * n)(*[q.data_ptr() for q in params])
     d.params = parr
     mma = E.token_mma_mode(ctx.cdt)        # (cdt: the context's arithmetic -- fp32s is a compute mode of the fp32 storage type)
-    nbytes = ctx.lib.vinet_token_encoder_workspace_mma(C.byref(d), mma)
+    attn = E.token_attn_mode(ctx.cdt)
+    if attn == L.TK_MMA_F32:
+        sfx, mode = "_mma", (mma,)
+    else:
+        sfx, mode = "_attn", (mma, attn)
+    nbytes = getattr(ctx.lib, "vinet_token_encoder_workspace" + sfx)(C.byref(d), *mode)
     if nbytes < 0:
-        L.check(-1, "vinet_token_encoder_workspace_mma")
+        L.check(-1, "vinet_token_encoder_workspace" + sfx)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=ctx.device)
     d.ws, d.ws_bytes = ws.data_ptr(), nbytes
     d.masks = E._ptr(masks)
@@ -171,7 +177,7 @@ def token_encoder_forward(ctx, tf, tokens, out=None, masks=None):
         out = E.Act(E.View.alloc(xv.B, xv.T, xv.H, xv.W, Efeat, ctx.dt, ctx.device))
     out.needs_grad = True
     assert out.v.same_dims(xv) and out.plain, "the encoder's output has its input's dims"
-    ctx.call("vinet_token_encoder_fwd_mma", C.byref(d), mma, C.byref(xv.ct()), C.byref(out.v.ct()), ctx.stream)
+    ctx.call("vinet_token_encoder_fwd" + sfx, C.byref(d), *mode, C.byref(xv.ct()), C.byref(out.v.ct()), ctx.stream)
     if ctx.recording:
         def bwd():
             dg = out.grad_view()
@@ -181,7 +187,7 @@ def token_encoder_forward(ctx, tf, tokens, out=None, masks=None):
             garr = (C.c_void_p * n)(*[E._ptr(g) for g in grads])
             d.grads, d.masks = garr, None
             # (d keeps parr / ws / step alive through the closure: the descriptor is the forward's, workspace included)
-            ctx.call("vinet_token_encoder_bwd_mma", C.byref(d), mma, C.byref(dg.ct()), C.byref(dx.ct()) if dx else None, ctx.stream)
+            ctx.call("vinet_token_encoder_bwd" + sfx, C.byref(d), *mode, C.byref(dg.ct()), C.byref(dx.ct()) if dx else None, ctx.stream)
             E._note_param_grad(ctx, *params)
             if dx is not None:
                 tokens.mark_grad_ready()

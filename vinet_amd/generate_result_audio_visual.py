@@ -213,7 +213,11 @@ def build_parser():
     p.add_argument('--token_mma', default="fp32", choices=["fp32", "bf16x3", "bf16", "match"],
                    help="BUILD-DEFINED, only with --token_fusion True: arithmetic of the token encoder's linear products.  fp32 (default): exact "
                         "products on the fp32 MFMA; bf16x3: the split-bf16 arithmetic of the fp32s convs; bf16; match: the one of --compute_dtype "
-                        "(fp32 -> fp32, fp32s -> bf16x3, bf16 -> bf16).  Attention, softmax and LayerNorm stay fp32")
+                        "(fp32 -> fp32, fp32s -> bf16x3, bf16 -> bf16).  Attention has --token_attn; softmax and LayerNorm stay fp32")
+    p.add_argument('--token_attn', default="fp32", choices=["fp32", "bf16x3", "bf16", "match"],
+                   help="BUILD-DEFINED, only with --token_fusion True: arithmetic of the token encoder's attention products (scores, P V and "
+                        "their gradients), the same four values as --token_mma.  fp32 (default): the fp32-MFMA kernels.  The softmax itself, "
+                        "the dropout masks and the saved softmax rows are fp32 in every mode")
     p.add_argument('--compute_dtype', default="fp32s", choices=["bf16", "fp32", "fp32s"],
                    help="arithmetic of the HIP path.  Default fp32s (split-bf16 products, fp32 tensors): INSIDE the reference contract -- maps within "
                         "1e-3 of the PyTorch-CPU path, exact argmax.  bf16 is the throughput mode (2.9x faster; maps within 2.5e-2, gradients of the "
@@ -237,6 +241,7 @@ def main(argv=None):
     dev = torch.device('cuda')
     engine.set_default_dtype(args.compute_dtype)
     engine.configure(token_mma=args.token_mma)
+    engine.set_token_attn(args.token_attn)
     kw = dict(transformer_in_channel=args.transformer_in_channel, nhead=args.nhead, use_upsample=bool(args.decoder_upsample),
               num_hier=args.num_hier, num_clips=args.clip_size)
     if args.token_fusion:

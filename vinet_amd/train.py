@@ -85,7 +85,11 @@ def build_parser():
     p.add_argument('--token_mma', default="fp32", choices=["fp32", "bf16x3", "bf16", "match"],
                    help="BUILD-DEFINED, only with --token_fusion True: arithmetic of the token encoder's linear products.  fp32 (default): exact "
                         "products on the fp32 MFMA; bf16x3: the split-bf16 arithmetic of the fp32s convs; bf16; match: the one of --compute_dtype "
-                        "(fp32 -> fp32, fp32s -> bf16x3, bf16 -> bf16).  Attention, softmax and LayerNorm stay fp32")
+                        "(fp32 -> fp32, fp32s -> bf16x3, bf16 -> bf16).  Attention has --token_attn; softmax and LayerNorm stay fp32")
+    p.add_argument('--token_attn', default="fp32", choices=["fp32", "bf16x3", "bf16", "match"],
+                   help="BUILD-DEFINED, only with --token_fusion True: arithmetic of the token encoder's attention products (scores, P V and "
+                        "their gradients), the same four values as --token_mma.  fp32 (default): the fp32-MFMA kernels.  The softmax itself, "
+                        "the dropout masks and the saved softmax rows are fp32 in every mode")
     p.add_argument('--synthetic_steps', default=20, type=int, help="steps per epoch with --dataset synthetic")
     p.add_argument('--sound_path_data', default="/ssd_scratch/cvit/samyak/data/", type=str,
                    help="root of the audio-visual sets (hard-coded in the reference: dataloader.py:127)")
@@ -234,6 +238,7 @@ def run(args, train_dataset=None, val_dataset=None):
     rank, world, local, device = parallel.init_from_env()
     engine.set_default_dtype(args.compute_dtype)
     engine.configure(token_mma=args.token_mma)
+    engine.set_token_attn(args.token_attn)
     if args.compute_dtype == "bf16" and rank == 0:
         print("train.py: --compute_dtype bf16 is the throughput mode: forward maps are 8e-3 .. 1.6e-2 from the reference's (contract: 1e-3) and "
               "encoder gradients are noisy; on the 48-step trajectory fixture it descends like the reference's own ensemble "
