@@ -411,6 +411,31 @@ int vinet_upsample2x_bwd(const VinetTensor* dy, const VinetTensor* dx, int32_t d
  * model.py:256-258): dx = [xf > 0] * upsample2x^T(dy), xf = the ReLU's output (the upsample's input, dx's extent).  Stores. */
 int vinet_upsample2x_bwd_relu(const VinetTensor* dy, const VinetTensor* dx, const VinetTensor* xf, int32_t dtype, void* stream);
 
+/* ----------------------------------------------------------------------
+ * The decoder tail behind the last upsample (csrc/decoder_tail.hip), one pass forward and one backward:
+ *   u [B, kT, H, W, 32] -> conv 32->32 (kT,1,1)/s(kT,1,1) (+ b_mid) -> ReLU -> a6 [B, 1, H, W, 32]
+ *                       -> conv 32->1 + b_head -> sigmoid -> out [B, H, W] fp32 (element strides sb, sh, sw)
+ * vinet_decoder_tail_fwd: w_mid / w_head are the FORWARD packs of the two convs exactly as vinet_conv3d gets them (bf16,
+ * vinet_pack_weights: [kT][32][32] and [1][32]); b_mid may be NULL, b_head not; a6 may be NULL (inference: not stored).  out and
+ * a6 hold the bits of vinet_conv3d (ReLU) + vinet_conv3d (8-channel-padded fp32 head, sigmoid) + vinet_export_ncdhw.
+ * vinet_decoder_tail_bwd: g = the gradient of `out` (fp32, own strides), w_mid_t the TRANSPOSED pack of the mid conv, w_head the
+ * forward pack of the head.  Writes dy_head [B, 1, H, W, 8] bf16 = bf16(g s (1 - s)) in channel 0 and zeros in channels 1..7,
+ * dz6 (a6's extent) = [a6 > 0] bf16(w_head dy_head), du (u's extent) = dz6 . W_mid per tap -- the bits of vinet_import_ncdhw +
+ * vinet_act_bwd (sigmoid) + the head's data gradient + vinet_act_bwd (ReLU) + the kT per-tap data gradients.  du is STORED:
+ * `accumulate` must be 0.  The weight and bias gradients of both convs stay with vinet_conv3d_wgrad / vinet_channel_sum over
+ * (u, dz6) and (a6, dy_head).
+ * Served: bf16, kT in {2, 3, 4}, u.T == kT (one output frame, as in every decoder), every view in whole groups of 8 channels on 16-byte addresses, packs on
+ * 16-byte addresses, out / g on 4-byte addresses.  vinet_decoder_tail_ok: 1 if the forward call with these arguments is served, else 0
+ * with the reason in vinet_last_error; it never launches.  The entry points return -1 on what is not served and launch nothing.
+ * ---------------------------------------------------------------------- */
+int vinet_decoder_tail_ok(int32_t dtype, const VinetTensor* u, int32_t kT, const void* w_mid, const float* b_mid, const void* w_head,
+                          const float* b_head, const VinetTensor* a6, const float* out);
+int vinet_decoder_tail_fwd(int32_t dtype, const VinetTensor* u, int32_t kT, const void* w_mid, const float* b_mid, const void* w_head,
+                           const float* b_head, const VinetTensor* a6, float* out, int64_t sb, int64_t sh, int64_t sw, void* stream);
+int vinet_decoder_tail_bwd(int32_t dtype, const float* g, int64_t gsb, int64_t gsh, int64_t gsw, const float* out, int64_t sb,
+                           int64_t sh, int64_t sw, const VinetTensor* a6, int32_t kT, const void* w_mid_t, const void* w_head,
+                           const VinetTensor* dy_head, const VinetTensor* dz6, const VinetTensor* du, int32_t accumulate, void* stream);
+
 /* SoundNet's first conv (model.py:751: Conv2d(1, 16, (64,1), stride (2,1), padding (32,0))) as a pointwise conv over the
  * unfolded waveform: y[b, m, 0, 0, c] = x[b, stride*m - pad + c, 0, 0, channel 0], zero outside; x = [B][L][1][1][C>=1],
  * y = [B][(L + 2 pad - k)/stride + 1][1][1][k], k = y.C (a multiple of 8).  The conv's weight [N][1][k][1] is, flat, the

@@ -114,6 +114,9 @@ SIGNATURES = {
     "vinet_maxpool3d_kernel_name": [_PP, _PT, CAffine, _PT, _vp, C.c_char_p, _i32],
     "vinet_maxpool3d_bwd_kernel_name": [_PP, _PT, _vp, _PT, C.c_char_p, _i32],
     "vinet_upsample2x": [_PT, _PT, _i32, _vp],
+    "vinet_decoder_tail_ok": [_i32, _PT, _i32, _vp, _vp, _vp, _vp, _PT, _vp],
+    "vinet_decoder_tail_fwd": [_i32, _PT, _i32, _vp, _vp, _vp, _vp, _PT, _vp, _i64, _i64, _i64, _vp],
+    "vinet_decoder_tail_bwd": [_i32, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _PT, _i32, _vp, _vp, _PT, _PT, _PT, _i32, _vp],
     "vinet_unfold1d": [_PT, _PT, _i32, _i32, _i32, _vp],
     "vinet_upsample2x_bwd": [_PT, _PT, _i32, _i32, _vp],
     "vinet_upsample2x_bwd_relu": [_PT, _PT, _PT, _i32, _vp],

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "obj")
 LIB = os.path.join(HERE, "libvinet_hip.so")
-SOURCES = ["conv_api.hip", "conv_bf16.hip", "conv_bnb.hip", "conv_f32.hip", "conv_wgrad.hip", "wgrad_dma.hip", "wgrad_pp.hip", "wgrad_ts.hip", "conv_ts.hip", "wgrad_hs.hip", "wgrad_rs.hip", "wgrad_tf.hip", "conv_hs.hip", "layout.hip", "bn.hip", "pool.hip", "resample.hip", "loss_adam.hip", "metrics.hip", "emd.hip", "postproc.hip", "preproc.hip", "transformer.hip", "token_encoder.hip"]
+SOURCES = ["conv_api.hip", "conv_bf16.hip", "conv_bnb.hip", "conv_f32.hip", "conv_wgrad.hip", "wgrad_dma.hip", "wgrad_pp.hip", "wgrad_ts.hip", "conv_ts.hip", "wgrad_hs.hip", "wgrad_rs.hip", "wgrad_tf.hip", "conv_hs.hip", "layout.hip", "bn.hip", "pool.hip", "resample.hip", "loss_adam.hip", "metrics.hip", "emd.hip", "postproc.hip", "preproc.hip", "transformer.hip", "token_encoder.hip", "decoder_tail.hip"]
 import glob
 # every header of csrc/ and include/ is a dependency of every object (a stale object travelling to the GPU box is worse
 # than a rebuild of 20 files)
@@ -30,7 +30,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.j
 # in one of them would read in-flight data: the build FAILS on it instead of shipping silently wrong kernels.  Checked from
 # hipcc's own -Rpass-analysis=kernel-resource-usage remarks of the same compilation (pinned toolchain: ROCm 7.2 / clang 22).
 GUARDED = {"conv_bf16.hip": ("conv_pw_kernel",), "pool.hip": ("maxpool_bwd",), "bn.hip": ("bn_bwd_reduce_pool", "bn_bwd_apply_pool"),
-           "conv_bnb.hip": ()}     # (conv_bnb.hip: resource table only)
+           "conv_bnb.hip": (), "decoder_tail.hip": ()}     # (conv_bnb.hip, decoder_tail.hip: resource table only)
 RESOURCES = os.path.join(CSRC, "obj", "kernel_resources.json")
 
 

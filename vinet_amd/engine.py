@@ -41,10 +41,10 @@ _UNPACK_TABLES = {}
 _SIDE_STREAMS = {}
 
 # ----------------------------------------------------------------------------
-# configuration: ONE explicit entry point, engine.configure(**kw).  Nothing here reads the environment (the only
-# environment variable of the package is VINET_LIB, the path of another build of the library: _lib.py); tools and
-# bench.py pass `--cfg name=value,...` through configure().  The values live as module attributes (tests monkeypatch
-# them); config() returns the current set, which bench.py records in its JSON line.
+# configuration: ONE explicit entry point, engine.configure(**kw).  Nothing in it reads the environment (the environment
+# variables of the package are VINET_LIB, the path of another build of the library: _lib.py, and VINET_DECODER_TAIL, the A/B
+# switch DECODER_TAIL_FUSED below the table); tools and bench.py pass `--cfg name=value,...` through configure().  The values
+# live as module attributes (tests monkeypatch them); config() returns the current set, which bench.py records in its JSON line.
 # ----------------------------------------------------------------------------
 _CONFIG = dict(
     # weight gradients are off the backward critical path (only the optimizer consumes them): they run on a second
@@ -115,6 +115,19 @@ _CONFIG = dict(
 )
 globals().update(_CONFIG)
 _ABLATE, _ABLATE_TAGS = set(), []
+
+# The decoder tail behind the last upsample (conv 32->32 (kT,1,1)/s kT -> ReLU -> conv 32->1 + bias -> sigmoid -> map) as ONE launch
+# forward and ONE backward (csrc/decoder_tail.hip, decoder_tail_forward below) instead of three and seven: bit-identical results.
+# A module attribute with its own setter, not a _CONFIG key; VINET_DECODER_TAIL=0 in the environment, read once here, turns it
+# off for a whole process (A/B runs of one tree).
+DECODER_TAIL_FUSED = os.environ.get("VINET_DECODER_TAIL", "1") not in ("0", "false", "False", "")
+
+
+def set_decoder_tail_fused(on):
+    """switch the fused decoder tail on or off; returns the previous value"""
+    global DECODER_TAIL_FUSED
+    old, DECODER_TAIL_FUSED = DECODER_TAIL_FUSED, bool(on)
+    return old
 
 
 def configure(**kw):
@@ -563,6 +576,8 @@ class Ctx:
         self.lib_keeps = getattr(lib, "vinet_maxpool3d_keep_ok", None) is not None and hasattr(lib, "vinet_maxpool3d_keep")
         self.lib_pools_in_bn = (getattr(lib, "vinet_bn_bwd_pool_ok", None) is not None and hasattr(lib, "vinet_bn_bwd_reduce_pool")
                                 and hasattr(lib, "vinet_bn_bwd_apply_pool"))
+        self.lib_tail = (getattr(lib, "vinet_decoder_tail_ok", None) is not None and hasattr(lib, "vinet_decoder_tail_fwd")
+                         and hasattr(lib, "vinet_decoder_tail_bwd"))
         self._begin_backward()
 
     def _begin_backward(self, capturing=False):
@@ -1893,6 +1908,72 @@ def upsample2x_forward(ctx, x, dst=None):
             x.mark_grad_ready()
         ctx.record(bwd)
     return dst
+
+
+class TailMap:
+    """what decoder_tail_forward returns where a conv_forward chain returns the padded fp32 head Act: the saliency map itself, a
+    [B, H, W] fp32 tensor the fused kernel wrote (no export pass), and -- set by the root body before run_backward -- its gradient
+    `g` (fp32 [B, H, W], any strides), which the recorded backward reads in place (no import pass)"""
+    __slots__ = ("plane", "g")
+
+    def __init__(self, plane):
+        self.plane, self.g = plane, None
+
+
+def decoder_tail_forward(ctx, mid, head, u):
+    """u -> conv `mid` 32->32 (kT,1,1)/s(kT,1,1) -> ReLU -> conv `head` 32->1 + bias -> sigmoid as ONE launch (vinet_decoder_tail_fwd),
+    backward as one more (vinet_decoder_tail_bwd: dy_head, dz6, du) followed by the two convs' unchanged weight-gradient jobs and
+    bias sums.  mid, head: ConvPlans.  Returns a TailMap, or None where the pair does not serve the problem (switch off, not a bf16
+    context, a library without the entry points, another geometry, u with another consumer): the caller then runs the convs."""
+    uv, kT = u.v, mid.k[0]
+    if not (DECODER_TAIL_FUSED and ctx.lib_tail and ctx.dt == BF16 and ctx.cdt == BF16 and u.plain and uv.dt == BF16 and u.fold is None):
+        return None
+    if not (mid.temporal and mid.k == mid.s == (kT, 1, 1) and mid.p == (0, 0, 0) and (mid.Cin, mid.N) == (32, 32) and uv.T == kT
+            and head.pointwise and (head.Cin, head.N) == (32, 1) and head.bias is not None and uv.C == 32):
+        return None
+    rec = ctx.recording
+    if rec and not (u.needs_grad and writers_left(u) == 0 and not u.is_grad_ready()):
+        return None         # (the backward STORES u's gradient: it must be its only writer)
+    B, H, W, dev = uv.B, uv.H, uv.W, uv.device
+    plane = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    a6 = Act(View.alloc(B, 1, H, W, 32, BF16, dev), needs_grad=True) if rec else None
+    wm, wh = mid.packed(ctx, False), head.packed(ctx, False)
+    a6p = C.byref(a6.v.ct()) if a6 is not None else None
+    if not ctx.lib.vinet_decoder_tail_ok(BF16, C.byref(uv.ct()), kT, wm.data_ptr(), _ptr(mid.bias), wh.data_ptr(), _ptr(head.bias), a6p,
+                                         plane.data_ptr()):
+        return None
+    nvox = B * H * W
+    site = "32->32->1 k%dx1x1 in%dx%dx%dx%d" % (kT, B, uv.T, H, W)
+    note_reader(ctx, u)
+    ctx.call("vinet_decoder_tail_fwd", BF16, C.byref(uv.ct()), kT, wm.data_ptr(), _ptr(mid.bias), wh.data_ptr(), _ptr(head.bias), a6p,
+             plane.data_ptr(), H * W, W, 1, ctx.stream, tag="decoder_tail_fwd_kernel<%d> | fwd %s" % (kT, site),
+             work=dict(flops=2.0 * nvox * 32 * (32 * kT + 1), bytes=float(nvox * (64 * kT + (64 if rec else 0) + 4))))
+    tm = TailMap(plane)
+    if rec:
+        note_reader(ctx, a6)
+
+        def bwd():
+            g = tm.g
+            assert g is not None and g.dtype == torch.float32 and tuple(g.shape) == (B, H, W), "decoder tail: backward without the map's gradient"
+            dy = View.alloc(B, 1, H, W, EG[BF16], BF16, dev)         # the head's gradient, channel-padded 1 -> 8 for its weight gradient
+            dz, du = a6.grad_view(), u.grad_view()
+            ctx.call("vinet_decoder_tail_bwd", BF16, g.data_ptr(), g.stride(0), g.stride(1), g.stride(2), plane.data_ptr(), H * W, W, 1,
+                     C.byref(a6.v.ct()), kT, mid.packed(ctx, True).data_ptr(), wh.data_ptr(), C.byref(dy.ct()), C.byref(dz.ct()),
+                     C.byref(du.ct()), 0, ctx.stream, tag="decoder_tail_bwd_kernel<%d> | bwd %s" % (kT, site),
+                     work=dict(flops=2.0 * nvox * 32 * (32 * kT + 1), bytes=float(nvox * (4 + 4 + 64 + 16 + 64 + 64 * kT))))
+            a6.mark_grad_ready()
+            u.mark_grad_ready()
+            tm.g = None
+            # bias sums and weight gradients of both convs: the operands and launches of _conv_backward
+            for plan, x, d in ((head, a6, dy), (mid, u, dz)):
+                if plan.bias is not None and plan.bias.requires_grad:
+                    _bias_grad(ctx, plan, d)
+                if plan.wants_wgrad():
+                    for w_ in plan.grad_targets():
+                        _param_grad(w_)
+                    _schedule_wgrad(ctx, _WgradJob(ctx, plan, x, d, nvox, True, None, None))
+        ctx.record(bwd)
+    return tm
 
 
 def unfold1d_forward(ctx, x, k, stride, pad):

@@ -130,7 +130,7 @@ class _DecoderConvUp(nn.Module):
                 tail.append(ConvParams(cin, cout, kernel_size=(kt, 1, 1), stride=(kt, 1, 1), bias=bias))
         self.convtsp4 = nn.Sequential(*stage(192, 64, 5), *stage(64, 32, spec["k5"]), *tail, _Marker("sigmoid"))
 
-    # -- engine forward: returns the channel-padded fp32 head Act [B,1,H,W,Np] ----
+    # -- engine forward: returns the channel-padded fp32 head Act [B,1,H,W,Np], or the map itself (E.TailMap) ----
     def _conv_relu_up(self, ctx, conv, x, skip=None, cat=None):
         z = E.conv_forward(ctx, conv.plan(), x, act=L.ACT_RELU)
         zv = z.v
@@ -168,6 +168,11 @@ class _DecoderConvUp(nn.Module):
         z = self._conv_relu_up(ctx, self.convtsp4[0], z)
         z = self._conv_relu_up(ctx, self.convtsp4[3], z)
         convs = [m for m in list(self.convtsp4)[6:] if isinstance(m, ConvParams)]
+        if len(convs) == 2:
+            # conv -> ReLU -> head -> sigmoid in one launch where the engine serves it: the map itself, not the padded head
+            tm = E.decoder_tail_forward(ctx, convs[0].plan(), convs[1].plan(), z)
+            if tm is not None:
+                return tm
         for conv in convs[:-1]:
             z = E.conv_forward(ctx, conv.plan(), z, act=L.ACT_RELU)
         head = convs[-1]
@@ -223,6 +228,8 @@ class _MapBody:
             else:
                 acts.append(E.import_ncdhw(ectx, t, None, needs_grad=r))
         head = self.fwd(ectx, *acts)
+        if isinstance(head, E.TailMap):     # the fused decoder tail wrote the map; its backward reads the map's gradient in place
+            return [head.plane], (acts, head, [t.shape[1] for t in inputs])
         E.note_reader(ectx, head)       # (the seed of backward writes its gradient)
         hv = head.v
         assert hv.T == 1 and hv.dt == E.F32
@@ -236,10 +243,13 @@ class _MapBody:
         g = gouts[0]
         if g.dtype != torch.float32:
             g = g.float()
-        gv = head.grad_view()
-        ectx.call("vinet_import_ncdhw", g.data_ptr(), g.stride(0), 0, 0, g.stride(1), g.stride(2), 1, C.byref(gv.ct()),
-                  gv.dt, ectx.stream)
-        head.mark_grad_ready()
+        if isinstance(head, E.TailMap):
+            head.g = g
+        else:
+            gv = head.grad_view()
+            ectx.call("vinet_import_ncdhw", g.data_ptr(), g.stride(0), 0, 0, g.stride(1), g.stride(2), 1, C.byref(gv.ct()),
+                      gv.dt, ectx.stream)
+            head.mark_grad_ready()
         ectx.run_backward()
         outs = []
         for i, (a, c) in enumerate(zip(acts, cin)):
