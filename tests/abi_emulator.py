@@ -71,8 +71,11 @@ def wr(t, dt, val, accumulate=False):
         v[...] = _f2bf(val).reshape(v.shape)
 
 
-def affine(x, a, C_):
-    if a.scale:
+def affine(x, a, C_, fused=False):
+    """fused: the layout kernels' fmaf(x, scale, shift) -- the product is exact in float64, the sum is rounded there and once more to fp32"""
+    if a.scale and fused:
+        x = (x.astype(np.float64) * _f32(a.scale, C_) + _f32(a.shift, C_)).astype(np.float32)
+    elif a.scale:
         x = x * _f32(a.scale, C_) + _f32(a.shift, C_)
         x = x.astype(np.float32)
     if a.relu:
@@ -151,7 +154,7 @@ class AbiEmulator:
 
     def vinet_split_bf16(self, src, pre, hi, lo, stream):
         src, hi, lo = (t._obj if hasattr(t, "_obj") else t for t in (src, hi, lo))
-        v = affine(rd(src, F32), pre, src.C)
+        v = affine(rd(src, F32), pre, src.C, fused=True)
         h = _bf2f(_f2bf(v.reshape(-1))).reshape(v.shape)
         wr(hi, BF16, h)
         wr(lo, BF16, v - h)
@@ -453,7 +456,7 @@ class AbiEmulator:
 
     def vinet_export_ncdhw(self, src, src_dtype, pre, dst, sb, sc, st, sh, sw, accumulate, stream):
         src = _deref(src)
-        v = affine(rd(src, src_dtype), pre, src.C)
+        v = affine(rd(src, src_dtype), pre, src.C, fused=True)
         span = (src.B - 1) * sb + (src.C - 1) * sc + (src.T - 1) * st + (src.H - 1) * sh + (src.W - 1) * sw + 1
         raw = _f32(dst, span)
         d = np.lib.stride_tricks.as_strided(raw, (src.B, src.T, src.H, src.W, src.C), (sb * 4, st * 4, sh * 4, sw * 4, sc * 4))
@@ -462,7 +465,7 @@ class AbiEmulator:
 
     def vinet_copy_affine(self, src, src_dtype, pre, dst, dst_dtype, accumulate, stream):
         src, dst = _deref(src), _deref(dst)
-        wr(dst, dst_dtype, affine(rd(src, src_dtype), pre, src.C), bool(accumulate))
+        wr(dst, dst_dtype, affine(rd(src, src_dtype), pre, src.C, fused=True), bool(accumulate))
         return 0
 
     # -- BN ----------------------------------------------------------------------

@@ -1961,7 +1961,7 @@ def test_unfold1d(dt):
     assert lib.vinet_unfold1d(C.byref(xmk("gpu").ct()), C.byref(bad), dt, stride, pad, _stream()) < 0
 
 
-@pytest.mark.parametrize("cin", [8, 32, 64])
+@pytest.mark.parametrize("cin", [8, 16, 32, 64])
 def test_conv3d_wgrad_skinny(cin):
     """pointwise weight gradient with a channel-padded 8-wide dy (the 32 -> 1 head): the reduction kernel, on views with
     a channel offset and a voxel count that is not a multiple of anything"""
