@@ -89,8 +89,8 @@ def audio_frame_bounds(n_frames, fps, Fs, n_samples_total):
 def audio_excerpt(wav, start, end, win=MAX_AUDIO_WIN):
     """Hanning-windowed excerpt wav[start:end+1] centred in `win` zeros (dataloader.py:95-121); wav: float32 [L] or [1,L]
     on the device (one upload per video), result float32 [win]."""
-    w = wav.reshape(-1)
-    assert w.dtype == torch.float32 and w.is_contiguous()
+    w = wav.reshape(-1).contiguous()          # (a strided view, such as one channel of [L, 2], is copied)
+    assert w.dtype == torch.float32
     out = torch.empty(win, dtype=torch.float32, device=w.device)
     L.check(L.get().vinet_audio_excerpt(w.data_ptr(), w.numel(), int(start), int(end), out.data_ptr(), win, E._stream_for(w.device)),
             "vinet_audio_excerpt")
